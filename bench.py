@@ -8,9 +8,16 @@ batch 256 per GPU, synthetic images resident in HBM, one process per GPU (weak s
 
 One "step" = re-derive the bf16 operand copies of the (possibly updated) fp32 weights -> forward ->
 softmax-CE gradient -> backward of every parameter [-> bucketed RCCL all-reduce of the gradients].
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying `roofline` for the dominant
-kernel class (the bf16 MFMA GEMM, timed with HIP events on the engine's stream) and `cpu_baseline`
-(the oracle's torch-CPU fp32 restatement of vit.py, timed on this box's host cores; rank 0, N=1 only).
+Prints ONE JSON line on rank 0 with the headline figure (`metric`, `value`, `unit`, `ms_per_step`, ...).  A plain run does only
+what that figure needs: set up, warm up, time the --steps steps, [write the outputs,] print.  --full adds the diagnostics that take
+runs of their own: `kernel_classes` / `gemm_shapes` / `roofline` for the dominant kernel class (the bf16 MFMA GEMM, timed with HIP
+events on the engine's stream over two more steps) and `cpu_baseline` (the oracle's torch-CPU fp32 restatement of vit.py, timed on
+the host cores; rank 0, N=1 only).
+
+--dump-outputs DIR (rank 0) writes what the last timed step computed, as float32 .npy files: `logits.npy` [batch, num_classes]
+(the forward's logits) and `grads_sample.npy` (the gradient arena, every parameter in table order, at a fixed seeded sample of
+at most 4M positions; all of it when smaller).  Inputs and weights are seeded, so two runs with the same arguments can be
+compared output for output.
 """
 from __future__ import annotations
 
@@ -98,6 +105,35 @@ def cpu_baseline(kw, seconds: float, batch: int = 16):
                       f"batch {batch}, {n} fwd+bwd steps in {el:.1f} s on {ncores} threads; TensorFlow itself is not installable here"}
 
 
+GRAD_SAMPLE = 1 << 22   # positions of the gradient arena written by --dump-outputs (16 MiB of float32)
+
+
+def grad_sample_index(n_params):
+    """The fixed, seeded, sorted positions of the gradient arena that --dump-outputs writes (None: all of it)."""
+    if n_params <= GRAD_SAMPLE:
+        return None
+    return np.unique(np.random.default_rng(0).integers(0, n_params, size=GRAD_SAMPLE, dtype=np.int64))
+
+
+def dump_outputs(out_dir, lib, h, n_params, b, num_classes):
+    """The outputs of the last timed step as a caller of the step would receive them: the logits of the forward and the gradient of
+    every parameter (the fp32 arena in table order; a fixed seeded sample of GRAD_SAMPLE positions when it is larger)."""
+    from vit_tensorflow import _native as N
+    os.makedirs(out_dir, exist_ok=True)
+    N.check(lib.vitx_sync(h))
+    logits = np.empty((b, num_classes), dtype=np.float32)
+    got = C.c_int64()
+    N.check(lib.vitx_debug_read(h, b"logits", 0, logits.ctypes.data_as(C.c_void_p), logits.size, C.byref(got)))
+    assert got.value == logits.size, (got.value, logits.shape)
+    grads = np.empty(n_params, dtype=np.float32)
+    N.check(lib.vitx_get_grads(h, grads.ctypes.data_as(C.c_void_p), n_params))
+    idx = grad_sample_index(n_params)
+    if idx is not None:
+        grads = grads[idx]
+    np.save(os.path.join(out_dir, "logits.npy"), logits)
+    np.save(os.path.join(out_dir, "grads_sample.npy"), grads)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -106,9 +142,13 @@ def main():
     ap.add_argument("--batch", type=int, default=256, help="images per GPU")
     ap.add_argument("--workload", default="vit_b16_224", choices=sorted(WORKLOADS))
     ap.add_argument("--compute", default="bf16", choices=["bf16", "fp32", "bf16x3"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the diagnostics (per-kernel-class timing + roofline of two more steps, the CPU baseline); off: the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (logits, a seeded sample of the gradients) to DIR/<name>.npy, float32")
     ap.add_argument("--cpu-seconds", type=float, default=25.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: leave out the per-kernel-class timing and the roofline")
     ap.add_argument("--graph", action="store_true", help="replay the step as one HIP graph (single GPU; the default launches kernel by kernel)")
     ap.add_argument("--bucket-mb", type=float, default=48.0)
     ap.add_argument("--grad-wire", default="fp32", choices=["fp32", "bf16"], help="dtype of the gradient all-reduce on the wire (N > 1)")
@@ -304,7 +344,10 @@ def main():
         out["config"]["exchange"] = {"buckets": int(st[0]), "sent_during_backward": int(st[1]), "bucket_mib": round(st[2] * 4 / (1 << 20), 1),
                                      "dense_launches_beside_a_collective": int(st[3])}
 
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, lib, h, model._n, b, kw["num_classes"])
+
+    if rank == 0 and args.full and not args.no_profile:
         try:   # per-kernel-class HIP-event timing of two more steps (outside the timed region)
             if sync:
                 N.check(lib.vitx_set_grad_ready_callback(h, C.cast(None, N.GRAD_READY_FN), None))
@@ -383,7 +426,7 @@ def main():
         except Exception as ex:   # never lose the headline line to a diagnostics problem
             out["roofline_error"] = repr(ex)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(WORKLOADS["vit_b16_224"], args.cpu_seconds)
         except Exception as ex:

@@ -31,3 +31,4 @@ def test_graft_entry_exposes_build_and_smoke():
 def test_bench_cli_parses():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "--gpus" in r.stdout and "--steps" in r.stdout and "--warmup" in r.stdout, r.stderr[-2000:]
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout, r.stdout

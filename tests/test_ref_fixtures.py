@@ -1,9 +1,9 @@
 """CPU tier: the oracle against fixtures produced by the REFERENCE'S OWN SOURCE (tests/golden/ref_*.npz, written by
-oracle/gen_ref_fixtures.py, which imports /root/reference/vit_tensorflow/{vit,deepvit,cait,parallel_vit,vit_with_patch_merger}.py
+oracle/gen_ref_fixtures.py, which imports the reference's vit_tensorflow/{vit,deepvit,cait,parallel_vit,vit_with_patch_merger}.py
 unmodified under oracle/tf_shim).  This is what pins parity: oracle/ref_numpy.py and oracle/ref_torch.py must reproduce the
-reference's logits, every variable's gradient and d(img) to float64 rounding.  Where /root/reference is present (this container,
-not the GPU box) the reference is also re-executed live and compared with the committed files, so the fixtures cannot drift from
-the source they claim to come from."""
+reference's logits, every variable's gradient and d(img) to float64 rounding.  Where build() has staged the reference's sources
+into oracle/_ref/ (oracle/build_ref.py; not on a GPU machine) the reference is also re-executed live and compared with the committed
+files, so the fixtures cannot drift from the source they claim to come from."""
 import os
 import subprocess
 import sys
@@ -64,7 +64,7 @@ def test_oracle_reproduces_reference_fixture_at_baseline_widths(case):
     assert np.abs(dimg.reshape(-1)[::997] - z["dimg_sample"]).max() <= 1e-6 * max(1.0, np.abs(dimg).max())
 
 
-@pytest.mark.skipif(not os.path.isdir(G.REF), reason="/root/reference is not present on this machine (GPU box)")
+@pytest.mark.skipif(not os.path.isdir(G.REF), reason="the reference's sources are not staged under oracle/_ref (build() stages them where a reference checkout exists)")
 @pytest.mark.parametrize("case", ["vit_small", "deepvit_small", "cait_small", "parallel_vit_2", "patch_merger_default"])
 def test_committed_fixture_is_what_the_reference_source_produces(case):
     """Re-run the reference's source under the shim in a fresh interpreter (the shim registers a fake `tensorflow` in sys.modules,
@@ -83,7 +83,7 @@ def test_committed_fixture_is_what_the_reference_source_produces(case):
     assert r.returncode == 0 and "OK" in r.stdout, r.stderr[-2000:]
 
 
-@pytest.mark.skipif(not os.path.isdir(G.REF), reason="/root/reference is not present on this machine (GPU box)")
+@pytest.mark.skipif(not os.path.isdir(G.REF), reason="the reference's sources are not staged under oracle/_ref (build() stages them where a reference checkout exists)")
 def test_committed_mpp_fixture_is_what_the_reference_source_produces():
     """tests/golden/ref_mpp_vit.npz = the reference's own mpp.py (MPP.call mpp.py:166-218, MPPLoss :90-131) re-run under the shim in a fresh
     interpreter, bit for bit."""
@@ -241,7 +241,7 @@ def test_mim_oracle_reproduces_reference_fixture(case):
     assert with_grad == {"mae_vit": 39, "mae_same_dim": 48, "simmim_vit": 2}[case]
 
 
-@pytest.mark.skipif(not os.path.isdir(G.REF), reason="/root/reference is not present on this machine (GPU box)")
+@pytest.mark.skipif(not os.path.isdir(G.REF), reason="the reference's sources are not staged under oracle/_ref (build() stages them where a reference checkout exists)")
 def test_t2t_weight_order_follows_keras_own_variables_then_sublayers():
     """Keras lists a Model's weights as its OWN tf.Variables first, then its sublayers' in attribute-creation order (Layer.weights =
     own trainable weights + children's).  Derived from the reference's source, not from the oracle: the order in which T2TViT.__init__

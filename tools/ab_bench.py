@@ -32,7 +32,7 @@ def main():
     for r in range(rounds):
         for side in ("A", "B"):
             env = dict(os.environ, VITX_LIB=libs[side])
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "10", "--warmup", "3", *extra],
+            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "10", "--warmup", "3", *extra],
                                env=env, capture_output=True, text=True)
             line = [l for l in p.stdout.splitlines() if l.startswith("{")]
             if p.returncode != 0 or not line:

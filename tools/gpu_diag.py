@@ -203,7 +203,7 @@ def stage_grads():
 
 def stage_bench_quick():
     for extra in ([], ["--workload", "vit_readme_256", "--batch", "64"]):
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline", *extra]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline", *extra]
         print(" ".join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)
         print(r.stdout[-6000:])
