@@ -382,6 +382,46 @@ int32_t vitx_distill_backward_input(vitx_distill_handle m, const float* dloss_ho
 /* "student_logits", "distill_logits" [b,num_classes], "distill_tokens" [b,dim] of the last forward */
 int32_t vitx_distill_read(vitx_distill_handle m, const char* which, float* out_host, int64_t cap_elems, int64_t* n_elems);
 
+/* ---- CrossViT (cross_vit.py:232-301): two ImageEmbedders, `depth` x [sm Transformer, lg Transformer, CrossTransformer], two summed
+ * mlp_heads.  A handle of its own (not a vitx_handle): parameter order in DESIGN.md section 7.  No data parallel, graph capture or
+ * in-library optimizer step: the device arenas are exposed for optimizers outside the library. */
+typedef struct vitx_crossvit_config {
+  int32_t image_size, num_classes, sm_dim, lg_dim;
+  int32_t sm_patch_size, sm_enc_depth, sm_enc_heads, sm_enc_mlp_dim, sm_enc_dim_head;
+  int32_t lg_patch_size, lg_enc_depth, lg_enc_heads, lg_enc_mlp_dim, lg_enc_dim_head;
+  int32_t cross_attn_depth, cross_attn_heads, cross_attn_dim_head, depth;
+  float dropout, emb_dropout;   /* cross_vit.py:252-253 */
+  float ln_eps;                 /* <= 0: Keras LayerNormalization default 1e-3 */
+  int32_t compute;              /* VITX_COMPUTE_*: the encoders' mode; the cross layers run in fp32 in every mode */
+  int32_t max_batch;
+  int32_t device_id;
+  int32_t reserved[8];
+} vitx_crossvit_config;
+typedef struct vitx_crossvit* vitx_crossvit_handle;
+/* host only, no GPU needed; errors carry the reference's assertion text */
+int32_t vitx_crossvit_param_table_size(const vitx_crossvit_config* cfg, int64_t* n_tensors, int64_t* n_elems);
+int32_t vitx_crossvit_param_table_entry(const vitx_crossvit_config* cfg, int64_t index, char* name, int32_t name_cap, int64_t shape[4],
+                                        int32_t* rank, int64_t* offset_elems);
+int32_t vitx_crossvit_create(const vitx_crossvit_config* cfg, vitx_crossvit_handle* out);
+int32_t vitx_crossvit_destroy(vitx_crossvit_handle m);
+int32_t vitx_crossvit_set_params(vitx_crossvit_handle m, const float* host_blob, int64_t n_elems);
+int32_t vitx_crossvit_get_params(vitx_crossvit_handle m, float* host_blob, int64_t n_elems);
+int32_t vitx_crossvit_get_grads(vitx_crossvit_handle m, float* host_blob, int64_t n_elems);
+/* device arenas (fp32, table order, every tensor 16-B aligned); call params_changed after writing the parameter arena */
+int32_t vitx_crossvit_params_dev(vitx_crossvit_handle m, float** dev_ptr, int64_t* n_elems);
+int32_t vitx_crossvit_grads_dev(vitx_crossvit_handle m, float** dev_ptr, int64_t* n_elems);
+int32_t vitx_crossvit_params_changed(vitx_crossvit_handle m);
+/* img [b, H, W, 3] NHWC, H and W <= image_size and divisible by both patch sizes; logits [b, num_classes] */
+int32_t vitx_crossvit_forward(vitx_crossvit_handle m, const float* img_host, int32_t b, int32_t H, int32_t W, int32_t training, uint64_t seed,
+                              float* logits_host);
+int32_t vitx_crossvit_forward_dev(vitx_crossvit_handle m, const float* img_dev, int32_t b, int32_t H, int32_t W, int32_t training, uint64_t seed,
+                                  float* logits_dev_or_null);
+/* VJP of the last forward for d(logits): overwrites the gradient arena; optional d(img) */
+int32_t vitx_crossvit_backward(vitx_crossvit_handle m, const float* dlogits_host, float* dimg_host_or_null);
+int32_t vitx_crossvit_backward_dev(vitx_crossvit_handle m, const float* dlogits_dev, float* dimg_dev_or_null);
+/* "sm_tokens" / "lg_tokens" [b, n, dim] (the multi-scale encoder's output), "sm_logits" / "lg_logits" [b, num_classes] */
+int32_t vitx_crossvit_read(vitx_crossvit_handle m, const char* which, float* out_host, int64_t cap_elems, int64_t* n_elems);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,23 @@ class DistillConfig(C.Structure):
     _fields_ = [("temperature", C.c_float), ("alpha", C.c_float), ("hard", C.c_int32), ("literal_loss", C.c_int32), ("reserved", C.c_int32 * 8)]
 
 
+class CrossViTConfig(C.Structure):
+    _fields_ = [
+        ("image_size", C.c_int32), ("num_classes", C.c_int32), ("sm_dim", C.c_int32), ("lg_dim", C.c_int32),
+        ("sm_patch_size", C.c_int32), ("sm_enc_depth", C.c_int32), ("sm_enc_heads", C.c_int32), ("sm_enc_mlp_dim", C.c_int32),
+        ("sm_enc_dim_head", C.c_int32),
+        ("lg_patch_size", C.c_int32), ("lg_enc_depth", C.c_int32), ("lg_enc_heads", C.c_int32), ("lg_enc_mlp_dim", C.c_int32),
+        ("lg_enc_dim_head", C.c_int32),
+        ("cross_attn_depth", C.c_int32), ("cross_attn_heads", C.c_int32), ("cross_attn_dim_head", C.c_int32), ("depth", C.c_int32),
+        ("dropout", C.c_float), ("emb_dropout", C.c_float),
+        ("ln_eps", C.c_float),
+        ("compute", C.c_int32),
+        ("max_batch", C.c_int32),
+        ("device_id", C.c_int32),
+        ("reserved", C.c_int32 * 8),
+    ]
+
+
 GRAD_READY_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64, C.c_int64)
 
 # every symbol include/vitx.h declares: (name, restype, argtypes)
@@ -164,6 +181,21 @@ SYMBOLS: List[Tuple[str, object, list]] = [
     ("vitx_distill_forward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_float, C.c_float, C.c_void_p]),
     ("vitx_distill_backward", C.c_int32, [C.c_void_p, C.c_void_p]),
     ("vitx_distill_read", C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, _P(C.c_int64)]),
+    ("vitx_crossvit_param_table_size", C.c_int32, [_P(CrossViTConfig), _P(C.c_int64), _P(C.c_int64)]),
+    ("vitx_crossvit_param_table_entry", C.c_int32, [_P(CrossViTConfig), C.c_int64, C.c_char_p, C.c_int32, _P(C.c_int64), _P(C.c_int32), _P(C.c_int64)]),
+    ("vitx_crossvit_create", C.c_int32, [_P(CrossViTConfig), _P(C.c_void_p)]),
+    ("vitx_crossvit_destroy", C.c_int32, [C.c_void_p]),
+    ("vitx_crossvit_set_params", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_crossvit_get_params", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_crossvit_get_grads", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_crossvit_params_dev", C.c_int32, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)]),
+    ("vitx_crossvit_grads_dev", C.c_int32, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)]),
+    ("vitx_crossvit_params_changed", C.c_int32, [C.c_void_p]),
+    ("vitx_crossvit_forward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]),
+    ("vitx_crossvit_forward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]),
+    ("vitx_crossvit_backward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("vitx_crossvit_backward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("vitx_crossvit_read", C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, _P(C.c_int64)]),
 ]
 
 _lib = None
@@ -202,6 +234,21 @@ def param_table(cfg: Config):
     rank, off = C.c_int32(), C.c_int64()
     for i in range(nt.value):
         check(l.vitx_param_table_entry(C.byref(cfg), i, name, 256, shape, C.byref(rank), C.byref(off)))
+        out.append((name.value.decode(), tuple(int(shape[k]) for k in range(rank.value)), int(off.value)))
+    return out, int(ne.value)
+
+
+def crossvit_param_table(cfg: CrossViTConfig):
+    """[(name, shape, offset)] of CrossViT's variables from the C library (host-only call; no GPU needed)."""
+    l = lib()
+    nt, ne = C.c_int64(), C.c_int64()
+    check(l.vitx_crossvit_param_table_size(C.byref(cfg), C.byref(nt), C.byref(ne)))
+    out = []
+    name = C.create_string_buffer(256)
+    shape = (C.c_int64 * 4)()
+    rank, off = C.c_int32(), C.c_int64()
+    for i in range(nt.value):
+        check(l.vitx_crossvit_param_table_entry(C.byref(cfg), i, name, 256, shape, C.byref(rank), C.byref(off)))
         out.append((name.value.decode(), tuple(int(shape[k]) for k in range(rank.value)), int(off.value)))
     return out, int(ne.value)
 

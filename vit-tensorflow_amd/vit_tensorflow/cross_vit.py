@@ -1,0 +1,207 @@
+"""Drop-in for vit_tensorflow/cross_vit.py: `CrossViT(...)` with the reference's constructor (cross_vit.py:233-253) and
+`__call__(img, training=True)` (cross_vit.py:290-301).  Both encoders' blocks, the final norms, the cross-attention layers and the
+heads run in HIP behind the C ABI (csrc/cross_vit.hip); parameters are in the order of DESIGN.md section 7."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Dict, List, Sequence
+
+import numpy as np
+
+from . import _native as N
+from ._model import VitxModel, _Weight
+
+
+class CrossViT:
+    def __init__(self, image_size, num_classes, sm_dim, lg_dim, sm_patch_size=12, sm_enc_depth=1, sm_enc_heads=8, sm_enc_mlp_dim=2048,
+                 sm_enc_dim_head=64, lg_patch_size=16, lg_enc_depth=4, lg_enc_heads=8, lg_enc_mlp_dim=2048, lg_enc_dim_head=64,
+                 cross_attn_depth=2, cross_attn_heads=8, cross_attn_dim_head=64, depth=3, dropout=0.1, emb_dropout=0.1,
+                 compute="fp32", max_batch=None, device=0, seed=None):
+        """Same arguments as the reference.  Engine-only keyword extras: compute='fp32'|'bf16'|'bf16x3', max_batch=int, device=int,
+        seed=int (the initialisers' generator)."""
+        assert image_size % sm_patch_size == 0, 'Image dimensions must be divisible by the patch size.'   # cross_vit.py:208
+        assert image_size % lg_patch_size == 0, 'Image dimensions must be divisible by the patch size.'
+        assert compute in ("fp32", "bf16", "bf16x3"), "compute must be 'fp32' (parity), 'bf16' (throughput) or 'bf16x3'"
+        cfg = N.CrossViTConfig()
+        for k, v in dict(image_size=image_size, num_classes=num_classes, sm_dim=sm_dim, lg_dim=lg_dim, sm_patch_size=sm_patch_size,
+                         sm_enc_depth=sm_enc_depth, sm_enc_heads=sm_enc_heads, sm_enc_mlp_dim=sm_enc_mlp_dim, sm_enc_dim_head=sm_enc_dim_head,
+                         lg_patch_size=lg_patch_size, lg_enc_depth=lg_enc_depth, lg_enc_heads=lg_enc_heads, lg_enc_mlp_dim=lg_enc_mlp_dim,
+                         lg_enc_dim_head=lg_enc_dim_head, cross_attn_depth=cross_attn_depth, cross_attn_heads=cross_attn_heads,
+                         cross_attn_dim_head=cross_attn_dim_head, depth=depth).items():
+            setattr(cfg, k, int(v))
+        cfg.dropout, cfg.emb_dropout = float(dropout), float(emb_dropout)
+        cfg.ln_eps = 1e-3   # Keras LayerNormalization default
+        cfg.compute = {"fp32": N.COMPUTE_FP32, "bf16": N.COMPUTE_BF16, "bf16x3": N.COMPUTE_BF16X3}[compute]
+        cfg.max_batch = int(max_batch or 0)
+        cfg.device_id = int(device)
+        self._cfg = cfg
+        self.compute = compute
+        self.image_size, self.num_classes = image_size, num_classes
+        self.sm_patch_size, self.lg_patch_size = sm_patch_size, lg_patch_size
+        self._handle = None
+        self._table, self._n = N.crossvit_param_table(cfg)
+        self._blob = np.zeros(self._n, dtype=np.float32)
+        self._device_newer = False
+        self._init_weights(np.random.default_rng(seed))
+
+    # ---- initialisers: tf.random.normal (cross_vit.py:216-217), Keras Dense glorot_uniform / zeros, LayerNormalization ones / zeros
+    def _init_weights(self, rng: np.random.Generator) -> None:
+        for name, shape, off in self._table:
+            n = int(np.prod(shape))
+            leaf = name.split(".")[-1]
+            if leaf in ("pos_embedding", "cls_token"):
+                v = rng.standard_normal(n)
+            elif leaf == "kernel":
+                lim = math.sqrt(6.0 / (shape[0] + shape[1]))
+                v = rng.uniform(-lim, lim, n)
+            elif leaf == "gamma":
+                v = np.ones(n)
+            else:  # bias / beta
+                v = np.zeros(n)
+            self._blob[off:off + n] = v.astype(np.float32)
+
+    # ---- handle management (rebuilt, weights kept, when a larger batch arrives)
+    def _ensure_handle(self, batch: int):
+        l = N.lib()
+        if self._handle is not None and batch <= self._cfg.max_batch:
+            return self._handle
+        if self._handle is not None:
+            self._pull_params()
+            N.check(l.vitx_crossvit_destroy(self._handle))
+            self._handle = None
+        self._cfg.max_batch = max(int(batch), int(self._cfg.max_batch))
+        h = C.c_void_p()
+        N.check(l.vitx_crossvit_create(C.byref(self._cfg), C.byref(h)))
+        self._handle = h
+        self._push_params()
+        return h
+
+    def _push_params(self):
+        if self._handle is not None:
+            N.check(N.lib().vitx_crossvit_set_params(self._handle, self._blob.ctypes.data_as(C.c_void_p), self._n))
+        self._device_newer = False
+
+    def _pull_params(self):
+        if self._handle is not None and self._device_newer:
+            N.check(N.lib().vitx_crossvit_get_params(self._handle, self._blob.ctypes.data_as(C.c_void_p), self._n))
+            self._device_newer = False
+
+    def params_changed(self):
+        """The device parameter arena (params_dev) was written by an optimizer outside the library."""
+        if self._handle is not None:
+            N.check(N.lib().vitx_crossvit_params_changed(self._handle))
+            self._device_newer = True
+
+    def params_dev(self):
+        """(device pointer, elements) of the fp32 parameter arena (table order, every tensor 16-B aligned)."""
+        p, n = C.c_void_p(), C.c_int64()
+        N.check(N.lib().vitx_crossvit_params_dev(self._ensure_handle(1), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def grads_dev(self):
+        p, n = C.c_void_p(), C.c_int64()
+        N.check(N.lib().vitx_crossvit_grads_dev(self._ensure_handle(1), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def __del__(self):
+        try:
+            if getattr(self, "_handle", None) is not None:
+                N.lib().vitx_crossvit_destroy(self._handle)
+                self._handle = None
+        except Exception:
+            pass
+
+    # ---- Keras-like surface
+    @property
+    def weights(self) -> List[_Weight]:
+        return [_Weight(self, n, s, o) for n, s, o in self._table]
+
+    trainable_variables = weights
+    trainable_weights = weights
+
+    def get_weights(self) -> List[np.ndarray]:
+        self._pull_params()
+        return [self._blob[o:o + int(np.prod(s))].reshape(s).copy() for _, s, o in self._table]
+
+    def set_weights(self, weights: Sequence[np.ndarray]) -> None:
+        assert len(weights) == len(self._table), f"expected {len(self._table)} arrays, got {len(weights)}"
+        for w, (n, s, o) in zip(weights, self._table):
+            a = np.asarray(w, dtype=np.float32)
+            assert a.shape == tuple(s), f"{n}: expected shape {tuple(s)}, got {a.shape}"
+            self._blob[o:o + a.size] = a.reshape(-1)
+        self._push_params()
+
+    def state_dict(self) -> Dict[str, np.ndarray]:
+        return {n: w for (n, _, _), w in zip(self._table, self.get_weights())}
+
+    def load_state_dict(self, sd: Dict[str, np.ndarray]) -> None:
+        self.set_weights([sd[n] for n, _, _ in self._table])
+
+    def save_weights(self, path: str) -> None:
+        """Weights by table name in one .npz."""
+        np.savez(VitxModel._npz_path(path), **self.state_dict())
+
+    def load_weights(self, path: str) -> None:
+        with np.load(VitxModel._npz_path(path)) as z:
+            self.load_state_dict({k: z[k] for k in z.files})
+
+    def count_params(self) -> int:
+        return int(self._n)
+
+    # ---- forward / backward
+    def __call__(self, img, training=True, seed=None, **_):
+        """CrossViT.call(img, training=True) (cross_vit.py:290).  img: NHWC numpy or torch; H and W at most image_size and divisible
+        by both patch sizes (the position embeddings are sliced, cross_vit.py:226)."""
+        x, proto = VitxModel._as_host(img)
+        assert x.ndim == 4 and x.shape[3] == 3, "expected NHWC images [b, H, W, 3]"
+        b, H, W, _ = x.shape
+        for p in (self.sm_patch_size, self.lg_patch_size):
+            assert H % p == 0 and W % p == 0, 'Image dimensions must be divisible by the patch size.'
+        h = self._ensure_handle(b)
+        self._img_shape = (b, H, W, 3)
+        out = np.empty((b, self.num_classes), dtype=np.float32)
+        seed = int(np.random.randint(0, 2 ** 31 - 1)) if seed is None else int(seed)
+        N.check(N.lib().vitx_crossvit_forward(h, x.ctypes.data_as(C.c_void_p), b, H, W, 1 if training else 0, seed,
+                                              out.ctypes.data_as(C.c_void_p)))
+        return VitxModel._like(out, proto)
+
+    call = __call__
+    predict = lambda self, img, **kw: self(img, training=False, **kw)
+
+    def backward(self, dlogits, want_dimg: bool = False):
+        """VJP of the last forward.  Returns ({name: grad}, dimg | None)."""
+        if self._handle is None:
+            raise N.VitxError(N.ERR_STATE, "backward requires a preceding forward")
+        d, _ = VitxModel._as_host(dlogits)
+        dimg = np.empty(self._img_shape, dtype=np.float32) if want_dimg else None
+        N.check(N.lib().vitx_crossvit_backward(self._handle, d.ctypes.data_as(C.c_void_p),
+                                               dimg.ctypes.data_as(C.c_void_p) if want_dimg else None))
+        g = np.empty(self._n, dtype=np.float32)
+        N.check(N.lib().vitx_crossvit_get_grads(self._handle, g.ctypes.data_as(C.c_void_p), self._n))
+        return {n: g[o:o + int(np.prod(s))].reshape(s) for n, s, o in self._table}, dimg
+
+    def read(self, which: str) -> np.ndarray:
+        """Tensors of the last forward for bisecting: 'sm_tokens' / 'lg_tokens' [b, n, dim], 'sm_logits' / 'lg_logits' [b, num_classes]."""
+        if self._handle is None:
+            raise N.VitxError(N.ERR_STATE, "read requires a preceding forward")
+        b, H, W, _ = self._img_shape
+        cap = b * max(self.num_classes, max((H // p) * (W // p) + 1 for p in (self.sm_patch_size, self.lg_patch_size)) *
+                      max(self._cfg.sm_dim, self._cfg.lg_dim))
+        buf, n = np.empty(cap, dtype=np.float32), C.c_int64()
+        N.check(N.lib().vitx_crossvit_read(self._handle, which.encode(), buf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
+        out = buf[:n.value]
+        if which.endswith("_logits"):
+            return out.reshape(b, self.num_classes)
+        dim = self._cfg.sm_dim if which.startswith("sm") else self._cfg.lg_dim
+        return out.reshape(b, -1, dim)
+
+    # ---- not provided for CrossViT: refuse instead of misbehaving
+    def comm_init(self, *a, **k):
+        raise NotImplementedError("CrossViT: data parallel is not supported (all-reduce grads_dev() outside the library)")
+
+    def optimizer_step(self, *a, **k):
+        raise NotImplementedError("CrossViT: no in-library optimizer step (update params_dev() outside the library, then params_changed())")
+
+    def capture_graph(self, *a, **k):
+        raise NotImplementedError("CrossViT: HIP graph capture is not supported")
