@@ -69,7 +69,13 @@ typedef struct vitx_config {
    * (patch_merge_layer > 0 ? patch_merge_layer : depth / 2) - 1 the tokens are merged to patch_merge_num_tokens by PatchMerger
    * (LayerNorm + learned-query attention pooling, vit_with_patch_merger.py:42-55,117,131-132). */
   int32_t patch_merge_layer, patch_merge_num_tokens;
-  int32_t reserved[5];
+  /* vit_for_small_dataset.ViT (vit_for_small_dataset.py:159-215): != 0 replaces the patch embedding by SPT -- the image concatenated with its four
+   * one-pixel shifts, unfolded, LayerNorm, Dense (:142-157) -- and every attention by LSA: softmax scale exp(temperature) with a learned per-layer
+   * scalar, diagonal of the scores masked (:88-121).  Needs variant VITX_VARIANT_VIT, num_parallel_branches <= 1 and patch_h == patch_w (the
+   * reference's SPT hands patch_size to p1 and p2, :147); dim_head in {16, 32, 64} and at most 288 tokens, else VITX_ERR_UNSUPPORTED.
+   * 0 (a zeroed struct) = off: the handle is exactly the ordinary one. */
+  int32_t small_dataset;
+  int32_t reserved[4];
 } vitx_config;
 
 typedef struct vitx_engine* vitx_handle;
@@ -173,6 +179,11 @@ int32_t vitx_head_backward(vitx_handle h, const float* dlogits_host, float* dx_h
 int32_t vitx_head_backward_dev(vitx_handle h, const float* dlogits_dev_or_null, float* dx_dev);
 int32_t vitx_embed_backward(vitx_handle h, const float* dtokens_host, float* dimg_host_or_null);
 int32_t vitx_embed_backward_dev(vitx_handle h, const float* dtokens_dev, float* dimg_dev_or_null);
+
+/* ---- SPT(dim, patch_size)(img) on its own (vit_for_small_dataset.py:142-157) on a small_dataset handle: Dense(LN(unfold(concat(x, shifts)))),
+ * [b, np, dim]; no cls token, no position rows.  Forward only. */
+int32_t vitx_spt_forward(vitx_handle h, const float* img_host, int32_t b, int32_t H, int32_t W, float* tokens_host);
+int32_t vitx_spt_forward_dev(vitx_handle h, const float* img_dev, int32_t b, int32_t H, int32_t W, float* tokens_dev);
 
 /* ---- encoder.patch_embedding.layers[1] on its own: the nn.Dense(units=dim) of vit.py:143 as the wrappers borrow it (mae.py:37,52;
  * simmim.py:79,92; mpp.py:200) -- rows of unfolded patches [rows, p1*p2*C] -> [rows, dim]; no cls token, no position embedding.

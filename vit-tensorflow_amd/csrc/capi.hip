@@ -68,6 +68,11 @@ int32_t vitx_param_table_entry(const vitx_config* cfg, int64_t index, char* name
 int32_t vitx_create(const vitx_config* cfg, vitx_handle* out) {
   CAPI_TRY
   if (!cfg || !out) return fail(VITX_ERR_INVALID, "null argument");
+  if (cfg->small_dataset) {   // what such a config can be refused for needs no device
+    std::string verr;
+    const int vrc = engine_check_small_dataset(*cfg, verr);
+    if (vrc != VITX_OK) return fail(vrc, verr);
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
     return fail(VITX_ERR_HIP, "no HIP device available: libvitx has no CPU fallback (the product path is HIP-only)");
@@ -178,6 +183,7 @@ int32_t vitx_forward_dev(vitx_handle h, const float* img_dev, int32_t b, int32_t
 int32_t vitx_set_patch_input(vitx_handle h, int32_t np) {
   if (!h) return fail(VITX_ERR_INVALID, "null handle");
   if (np < 0 || np > h->np_max) return fail(VITX_ERR_INVALID, "set_patch_input: np must be in [0, num_patches]");
+  if (np > 0 && h->cfg.small_dataset) return fail(VITX_ERR_UNSUPPORTED, "set_patch_input: small_dataset handles take images only");
   h->next_patch_np = np;
   return VITX_OK;
 }
@@ -225,6 +231,7 @@ int32_t vitx_forward_patches(vitx_handle h, const float* patches_host, int32_t b
                              float* logits_host) {
   CAPI_TRY
   if (!h || !patches_host || !logits_host) return fail(VITX_ERR_INVALID, "null argument");
+  if (h->cfg.small_dataset) return fail(VITX_ERR_UNSUPPORTED, "forward_patches: small_dataset handles take images only");   // (the staging buffer holds one image, not 5x patch rows)
   if (b <= 0 || b > h->cfg.max_batch) return fail(VITX_ERR_INVALID, "batch must be in [1, max_batch]");
   if (np <= 0 || np > h->np_max) return fail(VITX_ERR_INVALID, "forward_patches: np must be in [1, num_patches]");
   CAPI_HIP(hipMemcpyAsync(h->img_dev, patches_host, (size_t)b * np * h->pd * 4, hipMemcpyHostToDevice, h->stream));
@@ -343,6 +350,33 @@ int32_t vitx_embed_forward(vitx_handle h, const float* img_host, int32_t b, int3
   int rc = engine_embed_forward(h, h->img_dev, b, H, W, tmp, err);
   if (rc != VITX_OK) return fail(rc, err);
   CAPI_HIP(hipMemcpyAsync(tokens_host, tmp, (size_t)b * h->last_ntok * h->cfg.dim * 4, hipMemcpyDeviceToHost, h->stream));
+  CAPI_HIP(hipStreamSynchronize(h->stream));
+  return VITX_OK;
+  CAPI_CATCH
+}
+// SPT(dim, patch_size)(img) (vit_for_small_dataset.py:142-157)
+int32_t vitx_spt_forward_dev(vitx_handle h, const float* img_dev, int32_t b, int32_t H, int32_t W, float* tokens_dev) {
+  CAPI_TRY
+  if (!h || !img_dev || !tokens_dev) return fail(VITX_ERR_INVALID, "null argument");
+  std::string err;
+  int rc = engine_spt_forward(h, img_dev, b, H, W, tokens_dev, err);
+  if (rc != VITX_OK) return fail(rc, err);
+  return VITX_OK;
+  CAPI_CATCH
+}
+int32_t vitx_spt_forward(vitx_handle h, const float* img_host, int32_t b, int32_t H, int32_t W, float* tokens_host) {
+  CAPI_TRY
+  if (!h || !img_host || !tokens_host) return fail(VITX_ERR_INVALID, "null argument");
+  if (!h->cfg.small_dataset) return fail(VITX_ERR_UNSUPPORTED, "spt_forward: small_dataset handles only");
+  if (b <= 0 || b > h->cfg.max_batch) return fail(VITX_ERR_INVALID, "batch must be in [1, max_batch]");
+  if (H <= 0 || W <= 0 || H > h->cfg.image_h || W > h->cfg.image_w) return fail(VITX_ERR_INVALID, "image larger than the configured image_size");
+  CAPI_HIP(hipMemcpyAsync(h->img_dev, img_host, (size_t)b * H * W * h->cfg.channels * 4, hipMemcpyHostToDevice, h->stream));
+  std::string err;
+  float* tmp = h->g;   // [>= mp, d] fp32 scratch that no forward kernel touches
+  int rc = engine_spt_forward(h, h->img_dev, b, H, W, tmp, err);
+  if (rc != VITX_OK) return fail(rc, err);
+  const int np = (H / h->cfg.patch_h) * (W / h->cfg.patch_w);
+  CAPI_HIP(hipMemcpyAsync(tokens_host, tmp, (size_t)b * np * h->cfg.dim * 4, hipMemcpyDeviceToHost, h->stream));
   CAPI_HIP(hipStreamSynchronize(h->stream));
   return VITX_OK;
   CAPI_CATCH

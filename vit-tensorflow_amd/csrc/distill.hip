@@ -343,6 +343,7 @@ int32_t vitx_backward_distill(vitx_handle h, const float* dlogits_host, const fl
 int32_t vitx_distill_create(vitx_handle student, const vitx_distill_config* cfg, vitx_distill_handle* out) {
   D_TRY
   if (!student || !cfg || !out) return capi_fail(VITX_ERR_INVALID, "null argument");
+  if (student->cfg.small_dataset) return capi_fail(VITX_ERR_UNSUPPORTED, "distill_create: small_dataset students are not supported");
   std::string err;
   vitx_distill* m = nullptr;
   int rc = distill_create(student, *cfg, &m, err);

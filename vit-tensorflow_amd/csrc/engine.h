@@ -58,6 +58,7 @@ struct Dense {
 
 struct BlockParams {
   int64_t a_scale = -1, ln1_g = -1, ln1_b = -1;
+  int64_t temp = -1;               // LSA temperature (small_dataset handles)
   Dense qkv, q, kv, out;
   Dense qkvcat;   // CaiT patch stage, bf16 mode: operand copies of [to_q | to_kv] side by side (w = -1: no parameter of its own)
   bool has_out = true;
@@ -157,6 +158,11 @@ struct vitx_engine {
   int64_t pm_g = -1, pm_b = -1, pm_q = -1;
   float *pm_xn = nullptr, *pm_mean = nullptr, *pm_rstd = nullptr, *pm_attn = nullptr, *pm_dattn = nullptr, *pm_out = nullptr, *pm_dxn = nullptr,
         *pm_dxn2 = nullptr, *pm_dq = nullptr;
+
+  // small_dataset handles (vit_for_small_dataset.py): SPT LayerNorm parameters and statistics, the engine's own copy of the last image (the SPT
+  // VJP re-reads it; the caller's / the staging buffer may be rewritten before the backward), workspaces of the SPT / LSA parameter gradients
+  int64_t spt_g = -1, spt_b = -1;
+  float *spt_mean = nullptr, *spt_rstd = nullptr, *spt_img = nullptr, *spt_ws = nullptr, *lsa_ws = nullptr;
 
   // parameter handles
   int64_t pos = -1, cls = -1, head_g = -1, head_b = -1;
@@ -258,6 +264,7 @@ int comm_finish(vitx_engine* e, std::string& err);
 void comm_stats(vitx_engine* e, int64_t* out4);
 void comm_destroy(vitx_engine* e);
 
+int engine_check_small_dataset(const vitx_config& cfg, std::string& err);   // host only
 int engine_create(const vitx_config& cfg, vitx_engine** out, std::string& err);
 void engine_destroy(vitx_engine* e);
 // distill_token_dev [dim] (optional): DistillMixin.call (distill.py:16-44) -- the token is appended after the position embedding,
@@ -274,6 +281,7 @@ int engine_patch_tokens_forward(vitx_engine* e, const float* img_dev, int b, int
 int engine_patch_tokens_backward(vitx_engine* e, const float* dtokens_dev, std::string& err);
 // efficient.ViT shell (efficient.py:12-56): embedding in front of / pooling + mlp_head behind a caller-supplied transformer
 int engine_embed_forward(vitx_engine* e, const float* img_dev, int b, int H, int W, float* tokens_dev, std::string& err);
+int engine_spt_forward(vitx_engine* e, const float* img_dev, int b, int H, int W, float* tokens_dev, std::string& err);   // SPT(dim, patch_size)(img)
 int engine_patch_dense_forward(vitx_engine* e, const float* patches_dev, int rows, float* out_dev, std::string& err);
 int engine_head_forward(vitx_engine* e, const float* x_dev, int b, int n, float* logits_dev, std::string& err);
 int engine_head_backward(vitx_engine* e, const float* dlogits_dev, float* dx_dev, std::string& err);

@@ -31,7 +31,11 @@ std::string build_param_table(const vitx_config& c, std::vector<ParamDesc>& out)
     return "dim/depth/heads/dim_head/mlp_dim/num_classes must be positive";
   const int64_t d = c.dim, h = c.heads, dh = c.dim_head, m = c.mlp_dim, nc = c.num_classes, inner = h * dh;
   const int64_t np = (int64_t)(c.image_h / c.patch_h) * (c.image_w / c.patch_w);
-  const int64_t pd = (int64_t)c.patch_h * c.patch_w * c.channels;
+  const bool sd = c.small_dataset != 0;   // vit_for_small_dataset.py
+  if (sd && c.variant != VITX_VARIANT_VIT) return "small_dataset needs the ViT variant";
+  if (sd && c.num_parallel_branches > 1) return "small_dataset does not combine with num_parallel_branches";
+  if (sd && c.patch_h != c.patch_w) return "small_dataset needs a square patch (SPT passes patch_size to p1 and p2)";
+  const int64_t pd = (int64_t)c.patch_h * c.patch_w * c.channels * (sd ? 5 : 1);   // SPT: the image and its four shifts (vit_for_small_dataset.py:154)
   int64_t off = 0, aoff = 0;
   auto add = [&](const std::string& n, std::vector<int64_t> s) {
     ParamDesc p;
@@ -49,12 +53,17 @@ std::string build_param_table(const vitx_config& c, std::vector<ParamDesc>& out)
   if (merger && c.patch_merge_num_tokens <= 0) return "patch_merge_num_tokens must be positive";
   add("pos_embedding", {1, cait ? np : np + 1, d});
   if (!merger) add("cls_token", {1, 1, d});          // vit_with_patch_merger.ViT has no cls token (vit_with_patch_merger.py:163-166)
+  if (sd) {                                          // SPT: Rearrange, LayerNormalization, Dense (vit_for_small_dataset.py:146-150)
+    add("patch_embedding.norm.gamma", {pd});
+    add("patch_embedding.norm.beta", {pd});
+  }
   add("patch_embedding.kernel", {pd, d});
   add("patch_embedding.bias", {d});
   auto block = [&](const std::string& pre) {
     if (cait) add(pre + ".attn.scale", {1, 1, d});
     add(pre + ".attn.norm.gamma", {d});
     add(pre + ".attn.norm.beta", {d});
+    if (sd) add(pre + ".attn.temperature", {1});     // LSA.temperature (vit_for_small_dataset.py:94), ahead of to_qkv
     if (cait) {
       add(pre + ".attn.to_q.kernel", {d, inner});
       add(pre + ".attn.to_kv.kernel", {d, 2 * inner});
@@ -68,7 +77,7 @@ std::string build_param_table(const vitx_config& c, std::vector<ParamDesc>& out)
       add(pre + ".attn.reattn_norm.gamma", {h});
       add(pre + ".attn.reattn_norm.beta", {h});
     }
-    const bool project_out = !((c.variant == VITX_VARIANT_VIT || merger) && h == 1 && dh == d);  // vit.py:53
+    const bool project_out = sd || !((c.variant == VITX_VARIANT_VIT || merger) && h == 1 && dh == d);  // vit.py:53; LSA always projects (vit_for_small_dataset.py:99-102)
     if (project_out) {
       add(pre + ".attn.to_out.kernel", {inner, d});
       add(pre + ".attn.to_out.bias", {d});
@@ -120,6 +129,20 @@ std::string build_param_table(const vitx_config& c, std::vector<ParamDesc>& out)
   add("mlp_head.kernel", {d, nc});
   add("mlp_head.bias", {nc});
   return "";
+}
+
+// small_dataset configs: everything that can be refused without a device (vitx_create runs it before it looks for one)
+int engine_check_small_dataset(const vitx_config& cfg, std::string& err) {
+  std::vector<ParamDesc> t;
+  const std::string perr = build_param_table(cfg, t);
+  if (!perr.empty()) { err = perr; return VITX_ERR_INVALID; }
+  const int ntok = (cfg.image_h / cfg.patch_h) * (cfg.image_w / cfg.patch_w) + 1;
+  if (cfg.depth > 0 && !attn_lsa_supported(ntok, cfg.dim_head)) {   // no fall-back to another attention path (depth 0: the tokenizer alone, SPT)
+    err = "small_dataset: the LSA kernels need dim_head in {16, 32, 64} and 2 <= tokens <= " + std::to_string(LSA_N_MAX) + " (got dim_head " +
+          std::to_string(cfg.dim_head) + ", " + std::to_string(ntok) + " tokens)";
+    return VITX_ERR_UNSUPPORTED;
+  }
+  return VITX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1022,7 +1045,10 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
     av.ldq = av.ldk = av.ldv = 3 * inner;
     av.qb = av.kb = av.vb = (int64_t)nq * 3 * inner;
   }
-  if (use_fused_attn_x3(e, nq)) {
+  if (c.small_dataset) {   // LSA (vit_for_small_dataset.py:109-117): learned temperature, masked diagonal
+    Prof pr(e, "attn_lsa_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
+    launch_attn_lsa_fwd(ba.qkv, ba.o, ba.lse, T, b, nq, c.heads, c.dim_head, e->params + bp.temp, e->stream);
+  } else if (use_fused_attn_x3(e, nq)) {
     Prof pr(e, "attn_x3_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
     launch_attn_x3_fwd((const float*)ba.qkv, (float*)ba.o, ba.lse, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), e->stream);
   } else if (use_fused_attn(e, nq)) {
@@ -1314,7 +1340,11 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
     ag.dq = e->d_qkv; ag.dk = boff(e->d_qkv, inner, esz); ag.dv = boff(e->d_qkv, 2 * inner, esz);
     ag.lddq = ag.lddk = ag.lddv = 3 * inner;
     ag.dqb = ag.dkb = ag.dvb = (int64_t)nq * 3 * inner;
-    if (use_fused_attn_x3(e, nq)) {
+    if (c.small_dataset) {
+      Prof pr(e, "attn_lsa_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
+      launch_attn_lsa_bwd(ba.qkv, ba.o, d_o, ba.lse, e->dsum, e->d_qkv, T, b, nq, c.heads, c.dim_head, e->params + bp.temp, e->grads + bp.temp,
+                          e->lsa_ws, e->stream);
+    } else if (use_fused_attn_x3(e, nq)) {
       Prof pr(e, "attn_x3_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
       launch_attn_x3_bwd((const float*)ba.qkv, (const float*)ba.o, (const float*)d_o, ba.lse, (float*)e->d_qkv, b, nq, c.heads,
                          1.0f / std::sqrt((float)c.dim_head), e->stream);
@@ -1384,7 +1414,7 @@ static int engine_create_body(vitx_engine* e, const vitx_config& cfg, std::strin
   const bool cait = c.variant == VITX_VARIANT_CAIT;
   e->ntok_max = cait ? e->np_max : e->np_max + 1;        // rows of pos_embedding (the merger ViT keeps np + 1 rows and uses np)
   e->ntok_cap = cait ? e->ntok_max : e->ntok_max + 1;
-  e->pd = c.patch_h * c.patch_w * c.channels;
+  e->pd = c.patch_h * c.patch_w * c.channels * (c.small_dataset ? 5 : 1);
   e->pd_k = (int)round_up(e->pd, 64);
   e->nc_k = (int)round_up(c.num_classes, 64);
   if (c.dim > 4096) { err = "dim must be <= 4096"; return VITX_ERR_UNSUPPORTED; }   // (any width: rows that are not multiples of 4 floats take the scalar-tail kernels)
@@ -1394,6 +1424,10 @@ static int engine_create_body(vitx_engine* e, const vitx_config& cfg, std::strin
     return VITX_ERR_UNSUPPORTED;
   }
   if (cait && c.cls_depth < 0) { err = "cls_depth must be >= 0"; return VITX_ERR_INVALID; }
+  if (c.small_dataset) {
+    const int rc_sd = engine_check_small_dataset(c, err);
+    if (rc_sd != VITX_OK) return rc_sd;
+  }
   e->force_generic_gemm = env_flag("VITX_GENERIC_GEMM");
   e->force_generic_attn = env_flag("VITX_GENERIC_ATTN");
   if (const char* k = vitx_env("VITX_DEEPVIT_FUSED")) e->deepvit_fused = atoi(k) != 0;
@@ -1489,6 +1523,7 @@ static int engine_create_body(vitx_engine* e, const vitx_config& cfg, std::strin
       bp.a_scale = find_param(e, pre + ".attn.scale");
       bp.ln1_g = find_param(e, pre + ".attn.norm.gamma");
       bp.ln1_b = find_param(e, pre + ".attn.norm.beta");
+      bp.temp = find_param(e, pre + ".attn.temperature");
       if (cait) {
         // patch stage (no context tokens) in bf16 mode: one Dense on the concatenated operand copies of to_q and to_kv (build_convert_table)
         const bool cat = e->bf16 && nc == 0 && e->cait_qkv_cat && inner % 64 == 0 && !e->force_generic_gemm;   // (the fp32-FMA debug path reads the parameter tensors themselves)
@@ -1702,6 +1737,15 @@ static int engine_create_body(vitx_engine* e, const vitx_config& cfg, std::strin
     if ((rc = ring(e->rg_cs, e->cs_part, cs_bytes, 4)) != VITX_OK) return rc;
   }
   DALLOC(e->dsum, (size_t)B * c.heads * e->ntok_cap * 4 + 16, false);
+  if (c.small_dataset) {
+    e->spt_g = find_param(e, "patch_embedding.norm.gamma");
+    e->spt_b = find_param(e, "patch_embedding.norm.beta");
+    DALLOC(e->spt_mean, (size_t)e->mpp * 4, false);
+    DALLOC(e->spt_rstd, (size_t)e->mpp * 4, false);
+    DALLOC(e->spt_img, (size_t)B * c.image_h * c.image_w * c.channels * 4, false);
+    DALLOC(e->spt_ws, (size_t)spt_bwd_ws_elems(e->pd) * 4, false);
+    DALLOC(e->lsa_ws, (size_t)attn_lsa_ws_elems((int)B, e->ntok_cap, c.heads) * 4, false);
+  }
   DALLOC(e->zero_page, 256, false);
   DALLOC(e->tmp_f32, (size_t)rmax * std::max<int64_t>(d, e->pd) * 4, false);
   const int64_t maxfeat = std::max<int64_t>({(int64_t)d, 3LL * inner, (int64_t)m, (int64_t)e->pd_k, (int64_t)e->nc_k});
@@ -1907,6 +1951,7 @@ int engine_forward(vitx_engine* e, const float* img_dev, int b, int H, int W, in
   // patch Dense, t2t.py:74-75,106): the unfold is skipped, everything else is the ordinary forward
   const float* patches_in = e->fwd_patches;
   e->fwd_patches = nullptr;
+  if (c.small_dataset && (patches_in || extra)) { err = "small_dataset handles take images only (no patch rows, no distillation token)"; return VITX_ERR_UNSUPPORTED; }
   if (patches_in) {
     if (e->fwd_np <= 0 || e->fwd_np > e->np_max) { err = "forward_patches: np must be in [1, num_patches]"; return VITX_ERR_INVALID; }
     H = e->fwd_np * c.patch_h; W = c.patch_w;      // np x 1 patches: keeps b * H * W * C == b * np * pd for the staging buffers
@@ -1927,6 +1972,11 @@ int engine_forward(vitx_engine* e, const float* img_dev, int b, int H, int W, in
   prepare_patch_rows(e, (int64_t)b * np);
   if (patches_in) {
     launch_convert(patches_in, e->pd, e->patches, T, e->pd_k, b * np, e->pd, e->pd_k, e->stream);
+  } else if (c.small_dataset) {   // SPT: shifts + unfold + LayerNorm in one kernel (vit_for_small_dataset.py:152-155); the VJP re-reads the image
+    if (img_dev != e->spt_img) HIPCHK(hipMemcpyAsync(e->spt_img, img_dev, (size_t)b * H * W * c.channels * 4, hipMemcpyDeviceToDevice, e->stream));
+    Prof pr(e, "spt_fwd", 0, (double)b * H * W * c.channels * 4 + (double)b * np * e->pd_k * e->esz);
+    launch_spt_fwd(e->spt_img, e->patches, T, e->pd_k, e->spt_mean, e->spt_rstd, e->params + e->spt_g, e->params + e->spt_b, b, H, W, c.channels,
+                   c.patch_h, c.ln_eps, e->stream);
   } else {
     Prof pr(e, "patch_unfold", 0, (double)b * H * W * c.channels * 4 + (double)b * np * e->pd_k * e->esz);
     launch_unfold(img_dev, e->patches, T, b, H, W, c.channels, c.patch_h, c.patch_w, e->pd_k, e->stream);   // vit.py:142
@@ -2002,6 +2052,7 @@ static int shell_check(const vitx_engine* e, std::string& err) {
   const vitx_config& c = e->cfg;
   if (c.variant != VITX_VARIANT_VIT && c.variant != VITX_VARIANT_DEEPVIT) { err = "embed / head entry points: ViT / DeepViT handles only"; return VITX_ERR_UNSUPPORTED; }
   if (c.num_parallel_branches > 1) { err = "embed / head entry points: not for parallel_vit handles"; return VITX_ERR_UNSUPPORTED; }
+  if (c.small_dataset) { err = "embed / head entry points: not for small_dataset handles"; return VITX_ERR_UNSUPPORTED; }
   return VITX_OK;
 }
 
@@ -2036,10 +2087,36 @@ int engine_embed_forward(vitx_engine* e, const float* img_dev, int b, int H, int
   return VITX_OK;
 }
 
+// SPT(dim, patch_size)(img) (vit_for_small_dataset.py:142-157): Dense(LN(unfold(concat(x, shifts)))) -> [b, np, dim], no cls token, no position
+// rows.  Forward only.
+int engine_spt_forward(vitx_engine* e, const float* img_dev, int b, int H, int W, float* tokens_dev, std::string& err) {
+  const vitx_config& c = e->cfg;
+  if (!c.small_dataset) { err = "spt_forward: small_dataset handles only"; return VITX_ERR_UNSUPPORTED; }
+  if (b <= 0 || b > c.max_batch) { err = "batch must be in [1, max_batch]"; return VITX_ERR_INVALID; }
+  if (H <= 0 || W <= 0 || H > c.image_h || W > c.image_w || H % c.patch_h || W % c.patch_w) {
+    err = "Image dimensions must be divisible by the patch size.";
+    return VITX_ERR_INVALID;
+  }
+  const int np = (H / c.patch_h) * (W / c.patch_w);
+  if (e->params_dirty) engine_refresh_weights(e);
+  prepare_patch_rows(e, (int64_t)b * np);
+  {
+    Prof pr(e, "spt_fwd", 0, (double)b * H * W * c.channels * 4 + (double)b * np * e->pd_k * e->esz);
+    launch_spt_fwd(img_dev, e->patches, e->bf16, e->pd_k, e->spt_mean, e->spt_rstd, e->params + e->spt_g, e->params + e->spt_b, b, H, W, c.channels,
+                   c.patch_h, c.ln_eps, e->stream);
+  }
+  EpiParams ep;
+  ep.out = tokens_dev; ep.ldo = c.dim;
+  dense_fwd(e, e->patches, e->pd_k, b * np, e->patch, EPI_STORE_F32, ep);
+  e->have_fwd = false; e->have_embed = false;   // e->patches no longer describes a forward that can be differentiated
+  return VITX_OK;
+}
+
 // patch_embedding.layers[1] on its own (mae.py:37, simmim.py:79, mpp.py:200): nn.Dense(units=dim) (vit.py:143) on rows of unfolded
 // patches [rows, p1*p2*C] -> [rows, dim], no cls token, no position embedding.  Forward only.
 int engine_patch_dense_forward(vitx_engine* e, const float* patches_dev, int rows, float* out_dev, std::string& err) {
   const vitx_config& c = e->cfg;
+  if (c.small_dataset) { err = "patch_dense_forward: not for small_dataset handles (vitx_spt_forward is their tokenizer)"; return VITX_ERR_UNSUPPORTED; }
   if (rows <= 0 || (int64_t)rows > (int64_t)c.max_batch * e->np_max) { err = "patch_dense_forward: rows must be in [1, max_batch * num_patches]"; return VITX_ERR_INVALID; }
   if (e->params_dirty) engine_refresh_weights(e);
   prepare_patch_rows(e, rows);
@@ -2145,6 +2222,7 @@ int engine_embed_backward(vitx_engine* e, const float* dtokens_dev, float* dimg_
 int engine_transformer_forward(vitx_engine* e, const float* tokens_dev, int b, int n, int training, uint64_t seed, float* out_dev, std::string& err) {
   const vitx_config& c = e->cfg;
   if (c.variant == VITX_VARIANT_CAIT || c.variant == VITX_VARIANT_PATCH_MERGER) { err = "transformer_forward: ViT / DeepViT only"; return VITX_ERR_UNSUPPORTED; }
+  if (c.small_dataset) { err = "transformer_forward: not for small_dataset handles"; return VITX_ERR_UNSUPPORTED; }
   if (b <= 0 || b > c.max_batch || n <= 0 || n > e->ntok_cap) { err = "transformer_forward: b or n out of range"; return VITX_ERR_INVALID; }
   ensure_geometry(e, b, n);
   if (e->params_dirty) engine_refresh_weights(e);
@@ -2192,6 +2270,7 @@ int engine_patch_tokens_forward(vitx_engine* e, const float* img_dev, int b, int
                                 std::string& err) {
   const vitx_config& c = e->cfg;
   if (c.variant == VITX_VARIANT_CAIT || c.variant == VITX_VARIANT_PATCH_MERGER) { err = "patch_tokens_forward: ViT / DeepViT only"; return VITX_ERR_UNSUPPORTED; }
+  if (c.small_dataset) { err = "patch_tokens_forward: not for small_dataset handles"; return VITX_ERR_UNSUPPORTED; }
   if (b <= 0 || b > c.max_batch) { err = "batch must be in [1, max_batch]"; return VITX_ERR_INVALID; }
   if (H <= 0 || W <= 0 || H > c.image_h || W > c.image_w || H % c.patch_h || W % c.patch_w) {
     err = "Image dimensions must be divisible by the patch size.";
@@ -2376,7 +2455,14 @@ int engine_backward(vitx_engine* e, const float* dlogits_dev, float* dimg_dev, s
     if (!no_cls) launch_batch_reduce(e->g, b, ntok, d, 0, 1, e->grads + e->cls, e->stream);   // dcls = sum_b g[b,0]
     launch_sum_rows(e->grads + e->pos + (int64_t)tok_off * d, np, d, e->grads + e->patch.b, e->stream);   // db = sum over patch rows
   }
-  if (dimg_dev) {
+  if (c.small_dataset) {   // SPT VJP: the LayerNorm parameter gradients need d(rows) whether or not d(img) is asked for
+    EpiParams ep; ep.out = e->tmp_f32; ep.ldo = e->pd;
+    dense_dgrad(e, e->d_y, d, b * np, e->patch, EPI_STORE_F32, ep);
+    Prof pr(e, "spt_bwd", 0, (double)b * np * e->pd * 8);
+    launch_spt_bwd(e->spt_img, e->tmp_f32, e->pd, e->spt_mean, e->spt_rstd, e->params + e->spt_g, e->spt_ws, e->grads + e->spt_g, e->grads + e->spt_b,
+                   dimg_dev != nullptr, b, e->last_H, e->last_W, c.channels, c.patch_h, e->stream);
+    if (dimg_dev) launch_spt_dimg(e->tmp_f32, e->pd, dimg_dev, b, e->last_H, e->last_W, c.channels, c.patch_h, e->stream);
+  } else if (dimg_dev) {
     EpiParams ep; ep.out = e->tmp_f32; ep.ldo = e->pd;
     dense_dgrad(e, e->d_y, d, b * np, e->patch, EPI_STORE_F32, ep);
     if (e->last_from_patches) {   // the forward took patch rows: d(patches) [b, np, pd] goes out as it is

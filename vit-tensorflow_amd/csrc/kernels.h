@@ -88,6 +88,31 @@ void launch_attn_x3_bwd(const float* qkv, const float* o, const float* d_o, cons
 void launch_attn_bf16_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o, const float* lse, float* dsum_ws,
                           bf16_t* dqkv, int b, int n, int h, float scale, const bf16_t* zero_page, hipStream_t s);
 
+// ---------------------------------------------------------------- attn_lsa.hip
+// locality self-attention (vit_for_small_dataset.py:88-121) on packed qkv [b, n, 3, h, dh] (fp32 storage: exact fp32 FMA; bf16 storage: every product
+// on the bf16 matrix pipe with P / dS rounded to bf16 in front of the second products, fp32 softmax and accumulation): scores scaled by
+// exp(*temperature) (a device scalar in the parameter arena), diagonal masked, softmax, P v.  dim_head in {16, 32, 64}, 2 <= n <= LSA_N_MAX.
+constexpr int LSA_N_MAX = 288;
+bool attn_lsa_supported(int n, int dim_head);
+int64_t attn_lsa_ws_elems(int b, int n, int h);   // floats of part_ws (one temperature-gradient partial per workgroup)
+void launch_attn_lsa_fwd(const void* qkv, void* o, float* lse, int is_bf16, int b, int n, int h, int dim_head, const float* temperature, hipStream_t s);
+// dsum_ws: b * h * n floats; *dtemperature is overwritten (fixed-order two-pass sum)
+void launch_attn_lsa_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, float* dsum_ws, void* dqkv, int is_bf16, int b, int n, int h,
+                         int dim_head, const float* temperature, float* dtemperature, float* part_ws, hipStream_t s);
+
+// ---------------------------------------------------------------- spt.hip
+// shifted patch tokenization (vit_for_small_dataset.py:15-47,142-157): NHWC image -> LayerNorm'ed rows [b * np, 5 p p C] of the image concatenated
+// with its four one-pixel shifts (zero fill), unfolded; the shifted copies are index arithmetic on the one image.  mean / rstd: fp32 per row.
+void launch_spt_fwd(const float* img, void* rows, int rows_bf16, int64_t ldo, float* mean, float* rstd, const float* gamma, const float* beta, int b,
+                    int H, int W, int C, int p, float eps, hipStream_t s);
+int64_t spt_bwd_ws_elems(int feat);
+// LayerNorm VJP of the rows: d_rows [b * np, feat] (fp32, row stride ld) is replaced IN PLACE by the gradient of the un-normalised rows when
+// want_dx; dgamma / dbeta through partial rows in ws and a fixed-order second pass.
+void launch_spt_bwd(const float* img, float* d_rows, int64_t ld, const float* mean, const float* rstd, const float* gamma, float* ws, float* dgamma,
+                    float* dbeta, int want_dx, int b, int H, int W, int C, int p, hipStream_t s);
+// dimg[b, y, x, c] = the at most five entries of dx that read that pixel (gather: deterministic)
+void launch_spt_dimg(const float* dx, int64_t ld, float* dimg, int b, int H, int W, int C, int p, hipStream_t s);
+
 // ---------------------------------------------------------------- elementwise.hip
 void launch_unfold(const float* img, void* out, int out_bf16, int b, int H, int W, int C, int ph, int pw,
                    int64_t ldo, hipStream_t s);

@@ -444,6 +444,7 @@ extern "C" {
 int32_t vitx_mim_create(vitx_handle encoder, const vitx_mim_config* cfg, vitx_mim_handle* out) {
   MIM_TRY
   if (!encoder || !cfg || !out) return capi_fail(VITX_ERR_INVALID, "null argument");
+  if (encoder->cfg.small_dataset) return capi_fail(VITX_ERR_UNSUPPORTED, "mim_create: small_dataset encoders are not supported");
   std::string err;
   vitx_mim* m = nullptr;
   int rc = mim_create(encoder, *cfg, &m, err);

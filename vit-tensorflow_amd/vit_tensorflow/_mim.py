@@ -19,6 +19,9 @@ class MimWrapper:
                   decoder_dim_head=0, literal_loss=True, seed=None, mpp=None):
         assert masking_ratio > 0 and masking_ratio < 1, 'masking ratio must be kept between 0 and 1'   # mae.py:28, simmim.py:71
         assert isinstance(encoder, VitxModel), "encoder must be a vit_tensorflow ViT / DeepViT"
+        if encoder._cfg.small_dataset:   # the wrappers borrow the plain patch Dense and plain attention; SPT / LSA are neither
+            raise NotImplementedError(f"{type(self).__name__}: a vit_for_small_dataset.ViT encoder is not supported (its SPT tokenizer and LSA "
+                                      "attention are not what this wrapper borrows from an encoder)")
         self.masking_ratio = masking_ratio
         self.encoder = encoder
         self.image_size = pair(image_size)

@@ -158,7 +158,7 @@ class VitxModel:
 
     def _init_common(self, *, image_size, patch_size, num_classes, dim, depth, heads, mlp_dim, pool, dim_head, dropout,
                      emb_dropout, layer_dropout=0.0, cls_depth=0, num_parallel_branches=1, patch_merge_layer=None, patch_merge_num_tokens=8,
-                     compute="fp32", max_batch=None, device=0, seed=None, channels=3):
+                     small_dataset=0, compute="fp32", max_batch=None, device=0, seed=None, channels=3):
         ih, iw = pair(image_size)
         ph, pw = pair(patch_size)
         assert ih % ph == 0 and iw % pw == 0, 'Image dimensions must be divisible by the patch size.'
@@ -180,6 +180,7 @@ class VitxModel:
         cfg.num_parallel_branches = int(num_parallel_branches)
         cfg.patch_merge_layer = int(patch_merge_layer or 0)
         cfg.patch_merge_num_tokens = int(patch_merge_num_tokens)
+        cfg.small_dataset = int(small_dataset)
         cfg.max_batch = int(max_batch or 0)
         cfg.device_id = int(device)
         self._cfg = cfg
@@ -211,6 +212,8 @@ class VitxModel:
                 v = rng.uniform(-lim, lim, n)
             elif leaf == "gamma":
                 v = np.ones(n)
+            elif leaf == "temperature":
+                v = np.full(n, math.log(self.dim_head ** -0.5))   # vit_for_small_dataset.py:94
             elif leaf == "scale":
                 ind = int(name.split(".")[1])
                 v = np.full(n, layer_scale_init(ind + 1))

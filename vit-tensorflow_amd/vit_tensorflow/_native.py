@@ -39,7 +39,8 @@ class Config(C.Structure):
         ("device_id", C.c_int32),
         ("num_parallel_branches", C.c_int32),
         ("patch_merge_layer", C.c_int32), ("patch_merge_num_tokens", C.c_int32),
-        ("reserved", C.c_int32 * 5),
+        ("small_dataset", C.c_int32),
+        ("reserved", C.c_int32 * 4),
     ]
 
 
@@ -118,6 +119,8 @@ SYMBOLS: List[Tuple[str, object, list]] = [
     ("vitx_patch_unfold", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     ("vitx_embed_forward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     ("vitx_embed_forward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    ("vitx_spt_forward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    ("vitx_spt_forward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     ("vitx_patch_dense_forward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     ("vitx_head_forward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     ("vitx_head_forward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
