@@ -75,7 +75,13 @@ typedef struct vitx_config {
    * reference's SPT hands patch_size to p1 and p2, :147); dim_head in {16, 32, 64} and at most 288 tokens, else VITX_ERR_UNSUPPORTED.
    * 0 (a zeroed struct) = off: the handle is exactly the ordinary one. */
   int32_t small_dataset;
-  int32_t reserved[4];
+  /* cct.TransformerEncoderLayer (cct.py:139-174): != 0 changes the data flow of every block to x1 = x + attn(ln1(x)), x2 = ln2(x1),
+   * out = x2 + fc2(gelu(fc1(x2))) -- the second LayerNorm's result is the MLP input AND the residual stream -- and keeps to_out for heads == 1
+   * (cct.py:117-122 always projects).  The parameter table is the ordinary ViT's.  Needs variant VITX_VARIANT_VIT, num_parallel_branches <= 1,
+   * small_dataset == 0 and dropout == 0.  Such a handle serves vitx_cct_* through the device-pointer transformer entry; its image entry points
+   * return VITX_ERR_UNSUPPORTED.  0 (a zeroed struct) = off: the handle is exactly the ordinary one. */
+  int32_t cct_block;
+  int32_t reserved[3];
 } vitx_config;
 
 typedef struct vitx_engine* vitx_handle;
@@ -432,6 +438,52 @@ int32_t vitx_crossvit_backward(vitx_crossvit_handle m, const float* dlogits_host
 int32_t vitx_crossvit_backward_dev(vitx_crossvit_handle m, const float* dlogits_dev, float* dimg_dev_or_null);
 /* "sm_tokens" / "lg_tokens" [b, n, dim] (the multi-scale encoder's output), "sm_logits" / "lg_logits" [b, num_classes] */
 int32_t vitx_crossvit_read(vitx_crossvit_handle m, const char* which, float* out_host, int64_t cap_elems, int64_t* n_elems);
+
+/* ---- CCT (cct.py:307-345): convolutional tokenizer (Conv2D 'SAME' without bias, ReLU, MaxPool2D 'SAME', n_conv_layers times), optional
+ * positional embedding, num_layers encoder blocks of the CCT form (one vitx_config.cct_block engine), LayerNorm, sequence pooling, fc.
+ * A handle of its own; parameter order in DESIGN.md section 18.  Only the deterministic path (training falsy in the reference) exists. */
+enum { VITX_CCT_POS_LEARNABLE = 0, VITX_CCT_POS_SINE = 1, VITX_CCT_POS_NONE = 2 };
+typedef struct vitx_cct_config {
+  int32_t img_height, img_width;   /* pair(img_size), cct.py:319 */
+  int32_t n_input_channels, embedding_dim, n_conv_layers, kernel_size, stride, pooling_kernel_size, pooling_stride;
+  int32_t num_layers, num_heads;
+  int32_t dim_feedforward;         /* int(embedding_dim * mlp_ratio), cct.py:235 */
+  int32_t num_classes;
+  int32_t positional_embedding;    /* VITX_CCT_POS_*; SINE: a constant table built on the host, not a parameter */
+  int32_t in_planes;               /* filters of every conv layer but the last; <= 0: 64 (cct.py:182) */
+  float ln_eps;                    /* <= 0: Keras LayerNormalization default 1e-3 */
+  int32_t compute;                 /* VITX_COMPUTE_*: the encoder blocks' mode; tokenizer, final norm, pooling and fc keep fp32 storage */
+  int32_t max_batch;
+  int32_t device_id;
+  int32_t conv_chunk;              /* images per im2col + GEMM pass of the tokenizer; <= 0: sized from a fixed workspace budget */
+  int32_t reserved[8];
+} vitx_cct_config;
+typedef struct vitx_cct* vitx_cct_handle;
+/* host only, no GPU needed */
+int32_t vitx_cct_param_table_size(const vitx_cct_config* cfg, int64_t* n_tensors, int64_t* n_elems);
+int32_t vitx_cct_param_table_entry(const vitx_cct_config* cfg, int64_t index, char* name, int32_t name_cap, int64_t shape[4], int32_t* rank,
+                                   int64_t* offset_elems);
+int32_t vitx_cct_sequence_length(const vitx_cct_config* cfg, int32_t* n_tokens);   /* the 'SAME' geometry rule, no tokenizer run */
+int32_t vitx_cct_create(const vitx_cct_config* cfg, vitx_cct_handle* out);
+int32_t vitx_cct_destroy(vitx_cct_handle m);
+int32_t vitx_cct_set_params(vitx_cct_handle m, const float* host_blob, int64_t n_elems);
+int32_t vitx_cct_get_params(vitx_cct_handle m, float* host_blob, int64_t n_elems);
+int32_t vitx_cct_get_grads(vitx_cct_handle m, float* host_blob, int64_t n_elems);
+int32_t vitx_cct_params_dev(vitx_cct_handle m, float** dev_ptr, int64_t* n_elems);
+int32_t vitx_cct_grads_dev(vitx_cct_handle m, float** dev_ptr, int64_t* n_elems);
+int32_t vitx_cct_params_changed(vitx_cct_handle m);
+/* img [b, img_height, img_width, n_input_channels] NHWC; logits [b, num_classes] */
+int32_t vitx_cct_forward(vitx_cct_handle m, const float* img_host, int32_t b, float* logits_host);
+int32_t vitx_cct_forward_dev(vitx_cct_handle m, const float* img_dev, int32_t b, float* logits_dev_or_null);
+/* VJP of the last forward for d(logits): overwrites the gradient arena; d(img) only when asked for */
+int32_t vitx_cct_backward(vitx_cct_handle m, const float* dlogits_host, float* dimg_host_or_null);
+int32_t vitx_cct_backward_dev(vitx_cct_handle m, const float* dlogits_dev, float* dimg_dev_or_null);
+/* per-kernel-class timing of the steps between the two calls, as vitx_profile_begin / _end: the blocks' classes plus the composite's own
+ * (cct_im2col, cct_conv_gemm, cct_col2im, cct_relu_maxpool_fwd / _bwd, cct_seqpool_fwd / _bwd) */
+int32_t vitx_cct_profile_begin(vitx_cct_handle m);
+int32_t vitx_cct_profile_end(vitx_cct_handle m, vitx_kernel_stat* out, int32_t cap, int32_t* n_out);
+/* "tokens" [b, n, dim] (the tokenizer's output), "encoded" [b, n, dim] (after the final norm), "pool_weights" [b, n], "pooled" [b, dim] */
+int32_t vitx_cct_read(vitx_cct_handle m, const char* which, float* out_host, int64_t cap_elems, int64_t* n_elems);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,11 @@ std::string build_param_table(const vitx_config& c, std::vector<ParamDesc>& out)
   if (sd && c.variant != VITX_VARIANT_VIT) return "small_dataset needs the ViT variant";
   if (sd && c.num_parallel_branches > 1) return "small_dataset does not combine with num_parallel_branches";
   if (sd && c.patch_h != c.patch_w) return "small_dataset needs a square patch (SPT passes patch_size to p1 and p2)";
+  const bool cctb = c.cct_block != 0;   // cct.py:139-174
+  if (cctb && c.variant != VITX_VARIANT_VIT) return "cct_block needs the ViT variant";
+  if (cctb && c.num_parallel_branches > 1) return "cct_block does not combine with num_parallel_branches";
+  if (cctb && sd) return "cct_block does not combine with small_dataset";
+  if (cctb && c.dropout != 0.f) return "cct_block needs dropout == 0 (CCT hard-wires dropout_rate=0, cct.py:336)";
   const int64_t pd = (int64_t)c.patch_h * c.patch_w * c.channels * (sd ? 5 : 1);   // SPT: the image and its four shifts (vit_for_small_dataset.py:154)
   int64_t off = 0, aoff = 0;
   auto add = [&](const std::string& n, std::vector<int64_t> s) {
@@ -77,7 +82,7 @@ std::string build_param_table(const vitx_config& c, std::vector<ParamDesc>& out)
       add(pre + ".attn.reattn_norm.gamma", {h});
       add(pre + ".attn.reattn_norm.beta", {h});
     }
-    const bool project_out = sd || !((c.variant == VITX_VARIANT_VIT || merger) && h == 1 && dh == d);  // vit.py:53; LSA always projects (vit_for_small_dataset.py:99-102)
+    const bool project_out = sd || cctb || !((c.variant == VITX_VARIANT_VIT || merger) && h == 1 && dh == d);  // vit.py:53; LSA always projects (vit_for_small_dataset.py:99-102), so does CCT (cct.py:117-122)
     if (project_out) {
       add(pre + ".attn.to_out.kernel", {inner, d});
       add(pre + ".attn.to_out.bias", {d});
@@ -1099,6 +1104,18 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
     launch_layernorm_fwd(ba.ln2_src ? ba.ln2_src : ba.x_mid, d, e->params + bp.ln2_g, e->params + bp.ln2_b, ba.y2, T, d, ba.mean2, ba.rstd2, rows, d, c.ln_eps,
                          e->stream);
   }
+  // CCT block form (cct.py:165-172): norm1's result is the residual stream of the MLP branch -- fp32 storage holds it in y2 already, bf16 storage
+  // gets an fp32 copy of it (the residual stream never passes through bf16)
+  const float* mlp_resid = ba.x_mid;
+  if (c.cct_block) {
+    if (T) {
+      Prof pr(e, "layernorm_fwd", 0, lnb);
+      launch_layernorm_fwd(ba.x_mid, d, e->params + bp.ln2_g, e->params + bp.ln2_b, e->tmp_f32, 0, d, ba.mean2, ba.rstd2, rows, d, c.ln_eps, e->stream);
+      mlp_resid = e->tmp_f32;
+    } else {
+      mlp_resid = (const float*)ba.y2;
+    }
+  }
   {
     EpiParams ep; ep.out = ba.hpre; ep.ldo = m; ep.out2 = ba.act; ep.ldo2 = m;
     ep.nt_out = e->nt_mask & 1;
@@ -1117,7 +1134,7 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
                       rows, d, e->stream);
   } else {
     EpiParams ep;
-    ep.out = ba.x_out; ep.ldo = d; ep.resid = ba.x_mid; ep.ldr = d;
+    ep.out = ba.x_out; ep.ldo = d; ep.resid = mlp_resid; ep.ldr = d;
     if (bp.m_scale >= 0) { ep.scale = e->params + bp.m_scale; ep.out2 = ba.fm; ep.ldo2 = d; }
     dense_fwd(e, ba.act, m, rows, bp.fc2, EPI_BIAS_RESID, ep);                // vit.py:42,102
   }
@@ -1213,7 +1230,7 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
   // Order: the two consumers of d hpre (310 MB at ViT-B/16, just written) run right behind its producer; the fc2 weight gradient,
   // which reads other tensors (act, the branch gradient), follows them instead of sitting in between and pushing d hpre out of the
   // memory-side cache.  VITX_MLP_BWD_ORDER=0: fc2 weight gradient first (the order of round 1; same results either way).
-  const bool fc2_bias_in_ln = dbranch != e->d_br && !grouped;   // db_fc2 = column sums of g: fused into the LayerNorm backward pass below
+  const bool fc2_bias_in_ln = dbranch != e->d_br && !grouped && !c.cct_block;   // db_fc2 = column sums of g: fused into the LayerNorm backward pass below
   auto fc2_param_grads = [&]() {
     dense_wgrad(e, ba.act, m, dbranch, d, rows, bp.fc2, fork_fc2);
     side_note_read(e, dbranch == e->d_br ? e->rg_dbr : e->rg_glp);
@@ -1238,6 +1255,14 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
                       layernorm_bwd_scale_ok(d);
     void* ln_glp = fuse ? nullptr : next_glp();
     if (fuse) { side_rotate(e, e->rg_dbr, e->d_br); e->dbr_ready = key_attn; }
+    if (c.cct_block) {
+      // cct.py:165-172: out = x2 + mlp(x2) with x2 = norm1(x1), so d(x2) = d(out) + d(fc1 input) in fp32, and d(x1) is the LayerNorm VJP of it alone
+      launch_resid_add(e->g, e->d_y, T, e->tmp_f32, (int64_t)rows * d, e->stream);
+      // (the VJP kernels write their low-precision copy in dy's type, fp32 here: the bf16 copy of the new residual gradient is a pass of its own)
+      block_layernorm_bwd(e, e->tmp_f32, 0, d, ba.x_mid, ba.mean2, ba.rstd2, e->params + bp.ln2_g, nullptr, ln_gout, nullptr, e->grads + bp.ln2_g,
+                          e->grads + bp.ln2_b, nullptr, rows);
+      if (ln_glp) launch_convert(ln_gout, d, ln_glp, 1, d, rows, d, d, e->stream);
+    } else
     block_layernorm_bwd(e, e->d_y, T, d, ba.ln2_src ? ba.ln2_src : ba.x_mid, ba.mean2, ba.rstd2, e->params + bp.ln2_g, ln_gin, ln_gout, ln_glp,
                         e->grads + bp.ln2_g, e->grads + bp.ln2_b, fc2_bias_in_ln ? e->grads + bp.fc2.b : nullptr, rows, fuse ? &nb : nullptr);
   }
@@ -1951,6 +1976,7 @@ int engine_forward(vitx_engine* e, const float* img_dev, int b, int H, int W, in
   // patch Dense, t2t.py:74-75,106): the unfold is skipped, everything else is the ordinary forward
   const float* patches_in = e->fwd_patches;
   e->fwd_patches = nullptr;
+  if (c.cct_block) { err = "cct_block handles serve vitx_cct_* through the transformer entry points only"; return VITX_ERR_UNSUPPORTED; }
   if (c.small_dataset && (patches_in || extra)) { err = "small_dataset handles take images only (no patch rows, no distillation token)"; return VITX_ERR_UNSUPPORTED; }
   if (patches_in) {
     if (e->fwd_np <= 0 || e->fwd_np > e->np_max) { err = "forward_patches: np must be in [1, num_patches]"; return VITX_ERR_INVALID; }
@@ -2053,6 +2079,7 @@ static int shell_check(const vitx_engine* e, std::string& err) {
   if (c.variant != VITX_VARIANT_VIT && c.variant != VITX_VARIANT_DEEPVIT) { err = "embed / head entry points: ViT / DeepViT handles only"; return VITX_ERR_UNSUPPORTED; }
   if (c.num_parallel_branches > 1) { err = "embed / head entry points: not for parallel_vit handles"; return VITX_ERR_UNSUPPORTED; }
   if (c.small_dataset) { err = "embed / head entry points: not for small_dataset handles"; return VITX_ERR_UNSUPPORTED; }
+  if (c.cct_block) { err = "embed / head entry points: not for cct_block handles"; return VITX_ERR_UNSUPPORTED; }
   return VITX_OK;
 }
 
@@ -2271,6 +2298,7 @@ int engine_patch_tokens_forward(vitx_engine* e, const float* img_dev, int b, int
   const vitx_config& c = e->cfg;
   if (c.variant == VITX_VARIANT_CAIT || c.variant == VITX_VARIANT_PATCH_MERGER) { err = "patch_tokens_forward: ViT / DeepViT only"; return VITX_ERR_UNSUPPORTED; }
   if (c.small_dataset) { err = "patch_tokens_forward: not for small_dataset handles"; return VITX_ERR_UNSUPPORTED; }
+  if (c.cct_block) { err = "patch_tokens_forward: not for cct_block handles"; return VITX_ERR_UNSUPPORTED; }
   if (b <= 0 || b > c.max_batch) { err = "batch must be in [1, max_batch]"; return VITX_ERR_INVALID; }
   if (H <= 0 || W <= 0 || H > c.image_h || W > c.image_w || H % c.patch_h || W % c.patch_w) {
     err = "Image dimensions must be divisible by the patch size.";

@@ -113,6 +113,14 @@ void launch_spt_bwd(const float* img, float* d_rows, int64_t ld, const float* me
 // dimg[b, y, x, c] = the at most five entries of dx that read that pixel (gather: deterministic)
 void launch_spt_dimg(const float* dx, int64_t ld, float* dimg, int b, int H, int W, int C, int p, hipStream_t s);
 
+// ---------------------------------------------------------------- cct_tok.hip
+// CCT tokenizer behind the convolution (cct.py:196-200): out = MaxPool2D(k, st, 'SAME')(ReLU(conv)), conv [b, H, W, C] NHWC, out [b, ceil(H/st), ceil(W/st), C]
+// im2col rows [b * oh * ow, Kp] of a 'SAME' convolution (row order (ky, kx, c)); Kp >= k * k * C, columns beyond it are written as zeros
+void launch_cct_im2col(const float* x, float* rows, int b, int H, int W, int C, int k, int st, int Kp, hipStream_t s);
+void launch_cct_relu_maxpool_fwd(const float* conv, float* out, int b, int H, int W, int C, int k, int st, hipStream_t s);
+// its VJP in gather form (every element of dconv written; first maximum in row-major window order takes a window; no atomics)
+void launch_cct_relu_maxpool_bwd(const float* conv, const float* dout, float* dconv, int b, int H, int W, int C, int k, int st, hipStream_t s);
+
 // ---------------------------------------------------------------- elementwise.hip
 void launch_unfold(const float* img, void* out, int out_bf16, int b, int H, int W, int C, int ph, int pw,
                    int64_t ldo, hipStream_t s);

@@ -23,7 +23,14 @@ class VitxError(RuntimeError):
         self.message = msg
 
 
+class _ConfigTail(C.Union):
+    """The last four words of vitx_config.  include/vitx.h carved cct_block out of the first reserved word; `reserved` keeps its four-word view
+    here (reserved[0] is cct_block), so code that zeroes or inspects it by that name sees the layout it always saw."""
+    _fields_ = [("reserved", C.c_int32 * 4), ("cct_block", C.c_int32)]
+
+
 class Config(C.Structure):
+    _anonymous_ = ("_tail",)
     _fields_ = [
         ("variant", C.c_int32),
         ("image_h", C.c_int32), ("image_w", C.c_int32),
@@ -40,7 +47,7 @@ class Config(C.Structure):
         ("num_parallel_branches", C.c_int32),
         ("patch_merge_layer", C.c_int32), ("patch_merge_num_tokens", C.c_int32),
         ("small_dataset", C.c_int32),
-        ("reserved", C.c_int32 * 4),
+        ("_tail", _ConfigTail),
     ]
 
 
@@ -66,6 +73,21 @@ class MimConfig(C.Structure):
 
 class DistillConfig(C.Structure):
     _fields_ = [("temperature", C.c_float), ("alpha", C.c_float), ("hard", C.c_int32), ("literal_loss", C.c_int32), ("reserved", C.c_int32 * 8)]
+
+
+class CCTConfig(C.Structure):
+    _fields_ = [
+        ("img_height", C.c_int32), ("img_width", C.c_int32),
+        ("n_input_channels", C.c_int32), ("embedding_dim", C.c_int32), ("n_conv_layers", C.c_int32), ("kernel_size", C.c_int32),
+        ("stride", C.c_int32), ("pooling_kernel_size", C.c_int32), ("pooling_stride", C.c_int32),
+        ("num_layers", C.c_int32), ("num_heads", C.c_int32), ("dim_feedforward", C.c_int32), ("num_classes", C.c_int32),
+        ("positional_embedding", C.c_int32), ("in_planes", C.c_int32),
+        ("ln_eps", C.c_float), ("compute", C.c_int32), ("max_batch", C.c_int32), ("device_id", C.c_int32), ("conv_chunk", C.c_int32),
+        ("reserved", C.c_int32 * 8),
+    ]
+
+
+CCT_POS = {"learnable": 0, "sine": 1, "none": 2}
 
 
 class CrossViTConfig(C.Structure):
@@ -199,6 +221,24 @@ SYMBOLS: List[Tuple[str, object, list]] = [
     ("vitx_crossvit_backward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("vitx_crossvit_backward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("vitx_crossvit_read", C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, _P(C.c_int64)]),
+    ("vitx_cct_param_table_size", C.c_int32, [_P(CCTConfig), _P(C.c_int64), _P(C.c_int64)]),
+    ("vitx_cct_param_table_entry", C.c_int32, [_P(CCTConfig), C.c_int64, C.c_char_p, C.c_int32, _P(C.c_int64), _P(C.c_int32), _P(C.c_int64)]),
+    ("vitx_cct_sequence_length", C.c_int32, [_P(CCTConfig), _P(C.c_int32)]),
+    ("vitx_cct_create", C.c_int32, [_P(CCTConfig), _P(C.c_void_p)]),
+    ("vitx_cct_destroy", C.c_int32, [C.c_void_p]),
+    ("vitx_cct_set_params", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_cct_get_params", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_cct_get_grads", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_cct_params_dev", C.c_int32, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)]),
+    ("vitx_cct_grads_dev", C.c_int32, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)]),
+    ("vitx_cct_params_changed", C.c_int32, [C.c_void_p]),
+    ("vitx_cct_forward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("vitx_cct_forward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("vitx_cct_backward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("vitx_cct_backward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("vitx_cct_profile_begin", C.c_int32, [C.c_void_p]),
+    ("vitx_cct_profile_end", C.c_int32, [C.c_void_p, _P(KernelStat), C.c_int32, _P(C.c_int32)]),
+    ("vitx_cct_read", C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, _P(C.c_int64)]),
 ]
 
 _lib = None
@@ -280,3 +320,24 @@ def debug_switches():
     buf = C.create_string_buffer(need.value)
     check(lib().vitx_debug_switches(buf, need.value, None))
     return [tuple(line.split("\t", 3)) for line in buf.value.decode().splitlines()]
+
+
+def cct_param_table(cfg: CCTConfig):
+    """[(name, shape, offset)] of CCT's variables from the C library (host-only call; no GPU needed)."""
+    l = lib()
+    nt, ne = C.c_int64(), C.c_int64()
+    check(l.vitx_cct_param_table_size(C.byref(cfg), C.byref(nt), C.byref(ne)))
+    out = []
+    name = C.create_string_buffer(256)
+    shape = (C.c_int64 * 4)()
+    rank, off = C.c_int32(), C.c_int64()
+    for i in range(nt.value):
+        check(l.vitx_cct_param_table_entry(C.byref(cfg), i, name, 256, shape, C.byref(rank), C.byref(off)))
+        out.append((name.value.decode(), tuple(int(shape[k]) for k in range(rank.value)), int(off.value)))
+    return out, int(ne.value)
+
+
+def cct_sequence_length(cfg: CCTConfig) -> int:
+    n = C.c_int32()
+    check(lib().vitx_cct_sequence_length(C.byref(cfg), C.byref(n)))
+    return int(n.value)

@@ -1,0 +1,299 @@
+"""Drop-in for vit_tensorflow/cct.py: `CCT(...)` (cct.py:307-345) and the factories `cct_2 ... cct_16` (cct.py:16-61).  The convolutional
+tokenizer (Conv2D 'SAME' without bias, ReLU, MaxPool2D 'SAME'), the encoder blocks in the CCT form (the MLP residual leaves from the
+normalised stream, cct.py:165-172), the final norm, sequence pooling and fc run in HIP behind the C ABI (csrc/cct.hip, csrc/cct_tok.hip);
+parameters are in the order of DESIGN.md section 18.
+
+Only the deterministic path exists: `CCT.__call__(img, training=None)` with `training` falsy, which is what the reference computes there
+(Keras hands `training` down to every nested layer, so neither the attention dropout at 0.1 nor the stochastic depth at 0.1 that CCT
+hard-wires is active).  `training=True` needs both and raises NotImplementedError."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Dict, List, Sequence
+
+import numpy as np
+
+from . import _native as N
+from ._model import VitxModel, _Weight
+
+
+def pair(t):
+    return t if isinstance(t, tuple) else (t, t)
+
+
+# Pre-defined CCT Models
+__all__ = ['cct_2', 'cct_4', 'cct_6', 'cct_7', 'cct_8', 'cct_14', 'cct_16']
+
+
+def cct_2(*args, **kwargs):
+    return _cct(num_layers=2, num_heads=2, mlp_ratio=1, embedding_dim=128, *args, **kwargs)
+
+
+def cct_4(*args, **kwargs):
+    return _cct(num_layers=4, num_heads=2, mlp_ratio=1, embedding_dim=128, *args, **kwargs)
+
+
+def cct_6(*args, **kwargs):
+    return _cct(num_layers=6, num_heads=4, mlp_ratio=2, embedding_dim=256, *args, **kwargs)
+
+
+def cct_7(*args, **kwargs):
+    return _cct(num_layers=7, num_heads=4, mlp_ratio=2, embedding_dim=256, *args, **kwargs)
+
+
+def cct_8(*args, **kwargs):
+    return _cct(num_layers=8, num_heads=4, mlp_ratio=2, embedding_dim=256, *args, **kwargs)
+
+
+def cct_14(*args, **kwargs):
+    return _cct(num_layers=14, num_heads=6, mlp_ratio=3, embedding_dim=384, *args, **kwargs)
+
+
+def cct_16(*args, **kwargs):
+    return _cct(num_layers=16, num_heads=6, mlp_ratio=3, embedding_dim=384, *args, **kwargs)
+
+
+def _cct(num_layers, num_heads, mlp_ratio, embedding_dim, kernel_size=3, stride=None, *args, **kwargs):
+    stride = stride if stride is not None else max(1, (kernel_size // 2) - 1)   # cct.py:54
+    return CCT(num_layers=num_layers, num_heads=num_heads, mlp_ratio=mlp_ratio, embedding_dim=embedding_dim, kernel_size=kernel_size,
+               stride=stride, *args, **kwargs)
+
+
+def same_out(extent: int, stride: int) -> int:
+    """Output extent of a 'SAME' convolution / pooling: ceil(extent / stride)."""
+    return -(-int(extent) // int(stride))
+
+
+def sequence_length(img_size, n_conv_layers=1, stride=2, pooling_stride=2) -> int:
+    """Tokenizer.sequence_length (cct.py:204-209) from the 'SAME' geometry instead of a run on zeros."""
+    h, w = pair(img_size)
+    for _ in range(n_conv_layers):
+        h, w = same_out(same_out(h, stride), pooling_stride), same_out(same_out(w, stride), pooling_stride)
+    return h * w
+
+
+class CCT:
+    def __init__(self, img_size=224, embedding_dim=768, n_input_channels=3, n_conv_layers=1, kernel_size=7, stride=2, pooling_kernel_size=3,
+                 pooling_stride=2, *args, **kwargs):
+        """Same arguments as the reference: the eight above (cct.py:308-317) and, through **kwargs, TransformerClassifier's num_layers=12,
+        num_heads=12, mlp_ratio=4.0, num_classes=1000, positional_embedding='sine' (cct.py:217-230).  As in the reference, dropout_rate,
+        attention_dropout and stochastic_depth_rate are hard-wired (0, 0.1, 0.1: passing one of the last two raises TypeError, cct.py:336-338),
+        and unknown keywords (`padding`, `pooling_padding`, the usage example's `mlp_radio`) are swallowed.
+
+        positional_embedding='sine' is the reference's default, and the reference cannot run it: sinusoidal_embedding assigns into a tensor
+        (cct.py:271-272) and raises.  Here it is the table evidently meant -- p / 10000^(2 (i // 2) / dim), sin on even and cos on odd columns --
+        as a constant that is not part of the weights.
+
+        Engine-only keyword extras: compute='fp32'|'bf16'|'bf16x3', max_batch=int, device=int, seed=int (the initialisers' generator),
+        conv_chunk=int (images per im2col pass of the tokenizer; default: sized from a fixed workspace)."""
+        compute, max_batch, device, seed, conv_chunk = (kwargs.pop(k, v) for k, v in (("compute", "fp32"), ("max_batch", None), ("device", 0),
+                                                                                      ("seed", None), ("conv_chunk", 0)))
+        assert compute in ("fp32", "bf16", "bf16x3"), "compute must be 'fp32' (parity), 'bf16' (throughput) or 'bf16x3'"
+        if args:   # cct.py:330-339 passes them behind its own keywords: the first one lands on seq_pool
+            raise TypeError("TransformerClassifier() got multiple values for argument 'seq_pool'")
+        cls_kw = self._classifier_kwargs(**kwargs)
+        pe = cls_kw["positional_embedding"]
+        pe = pe if pe in ('sine', 'learnable', 'none') else 'sine'   # cct.py:233-234
+        img_height, img_width = pair(img_size)
+        cfg = N.CCTConfig()
+        for k, v in dict(img_height=img_height, img_width=img_width, n_input_channels=n_input_channels, embedding_dim=embedding_dim,
+                         n_conv_layers=n_conv_layers, kernel_size=kernel_size, stride=stride, pooling_kernel_size=pooling_kernel_size,
+                         pooling_stride=pooling_stride, num_layers=cls_kw["num_layers"], num_heads=cls_kw["num_heads"],
+                         dim_feedforward=int(embedding_dim * cls_kw["mlp_ratio"]), num_classes=cls_kw["num_classes"],
+                         positional_embedding=N.CCT_POS[pe], in_planes=64, conv_chunk=conv_chunk).items():
+            setattr(cfg, k, int(v))
+        cfg.ln_eps = 1e-3   # Keras LayerNormalization default
+        cfg.compute = {"fp32": N.COMPUTE_FP32, "bf16": N.COMPUTE_BF16, "bf16x3": N.COMPUTE_BF16X3}[compute]
+        cfg.max_batch = int(max_batch or 0)
+        cfg.device_id = int(device)
+        self._cfg = cfg
+        self.compute = compute
+        self.img_size = (int(img_height), int(img_width))
+        self.n_input_channels = int(n_input_channels)
+        self.num_classes = int(cls_kw["num_classes"])
+        self.positional_embedding = pe
+        self.embedding_dim = int(embedding_dim)
+        self._handle = None
+        self._table, self._n = N.cct_param_table(cfg)
+        self.sequence_length = N.cct_sequence_length(cfg)
+        self._blob = np.zeros(self._n, dtype=np.float32)
+        self._device_newer = False
+        self._init_weights(np.random.default_rng(seed))
+
+    @staticmethod
+    def _classifier_kwargs(num_layers=12, num_heads=12, mlp_ratio=4.0, num_classes=1000, positional_embedding='sine', **swallowed):
+        """What reaches TransformerClassifier.__init__ (cct.py:330-339): CCT passes sequence_length, embedding_dim, seq_pool, dropout_rate,
+        attention_dropout and stochastic_depth_rate itself, so a caller's copy of one of them is a duplicate keyword there."""
+        for k in ("seq_pool", "dropout_rate", "attention_dropout", "stochastic_depth_rate", "sequence_length"):
+            if k in swallowed:
+                raise TypeError(f"TransformerClassifier() got multiple values for keyword argument '{k}'")
+        return dict(num_layers=num_layers, num_heads=num_heads, mlp_ratio=mlp_ratio, num_classes=num_classes,
+                    positional_embedding=positional_embedding)
+
+    # ---- initialisers: Keras Conv2D / Dense glorot_uniform, zeros; LayerNormalization ones / zeros; truncated normal, stddev 0.2 (cct.py:252)
+    def _init_weights(self, rng: np.random.Generator) -> None:
+        for name, shape, off in self._table:
+            n = int(np.prod(shape))
+            leaf = name.split(".")[-1]
+            if leaf == "positional_emb":
+                v = rng.standard_normal(n)
+                bad = np.abs(v) > 2.0
+                while bad.any():   # tf.random.truncated_normal: values beyond two standard deviations are redrawn
+                    v[bad] = rng.standard_normal(int(bad.sum()))
+                    bad = np.abs(v) > 2.0
+                v = 0.2 * v
+            elif leaf == "kernel":
+                recv = int(np.prod(shape[:-2])) if len(shape) > 2 else 1
+                lim = math.sqrt(6.0 / (recv * shape[-2] + recv * shape[-1]))
+                v = rng.uniform(-lim, lim, n)
+            elif leaf == "gamma":
+                v = np.ones(n)
+            else:  # bias / beta
+                v = np.zeros(n)
+            self._blob[off:off + n] = v.astype(np.float32)
+
+    # ---- handle management (rebuilt, weights kept, when a larger batch arrives)
+    def _ensure_handle(self, batch: int):
+        l = N.lib()
+        if self._handle is not None and batch <= self._cfg.max_batch:
+            return self._handle
+        if self._handle is not None:
+            self._pull_params()
+            N.check(l.vitx_cct_destroy(self._handle))
+            self._handle = None
+        self._cfg.max_batch = max(int(batch), int(self._cfg.max_batch))
+        h = C.c_void_p()
+        N.check(l.vitx_cct_create(C.byref(self._cfg), C.byref(h)))
+        self._handle = h
+        self._push_params()
+        return h
+
+    def _push_params(self):
+        if self._handle is not None:
+            N.check(N.lib().vitx_cct_set_params(self._handle, self._blob.ctypes.data_as(C.c_void_p), self._n))
+        self._device_newer = False
+
+    def _pull_params(self):
+        if self._handle is not None and self._device_newer:
+            N.check(N.lib().vitx_cct_get_params(self._handle, self._blob.ctypes.data_as(C.c_void_p), self._n))
+            self._device_newer = False
+
+    def params_changed(self):
+        """The device parameter arena (params_dev) was written by an optimizer outside the library."""
+        if self._handle is not None:
+            N.check(N.lib().vitx_cct_params_changed(self._handle))
+            self._device_newer = True
+
+    def params_dev(self):
+        """(device pointer, elements) of the fp32 parameter arena (table order, every tensor 16-B aligned)."""
+        p, n = C.c_void_p(), C.c_int64()
+        N.check(N.lib().vitx_cct_params_dev(self._ensure_handle(1), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def grads_dev(self):
+        p, n = C.c_void_p(), C.c_int64()
+        N.check(N.lib().vitx_cct_grads_dev(self._ensure_handle(1), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def __del__(self):
+        try:
+            if getattr(self, "_handle", None) is not None:
+                N.lib().vitx_cct_destroy(self._handle)
+                self._handle = None
+        except Exception:
+            pass
+
+    # ---- Keras-like surface
+    @property
+    def weights(self) -> List[_Weight]:
+        return [_Weight(self, n, s, o) for n, s, o in self._table]
+
+    trainable_variables = weights
+    trainable_weights = weights
+
+    def get_weights(self) -> List[np.ndarray]:
+        self._pull_params()
+        return [self._blob[o:o + int(np.prod(s))].reshape(s).copy() for _, s, o in self._table]
+
+    def set_weights(self, weights: Sequence[np.ndarray]) -> None:
+        assert len(weights) == len(self._table), f"expected {len(self._table)} arrays, got {len(weights)}"
+        for w, (n, s, o) in zip(weights, self._table):
+            a = np.asarray(w, dtype=np.float32)
+            assert a.shape == tuple(s), f"{n}: expected shape {tuple(s)}, got {a.shape}"
+            self._blob[o:o + a.size] = a.reshape(-1)
+        self._push_params()
+
+    def state_dict(self) -> Dict[str, np.ndarray]:
+        return {n: w for (n, _, _), w in zip(self._table, self.get_weights())}
+
+    def load_state_dict(self, sd: Dict[str, np.ndarray]) -> None:
+        self.set_weights([sd[n] for n, _, _ in self._table])
+
+    def save_weights(self, path: str) -> None:
+        """Weights by table name in one .npz."""
+        np.savez(VitxModel._npz_path(path), **self.state_dict())
+
+    def load_weights(self, path: str) -> None:
+        with np.load(VitxModel._npz_path(path)) as z:
+            self.load_state_dict({k: z[k] for k in z.files})
+
+    def count_params(self) -> int:
+        return int(self._n)
+
+    # ---- forward / backward
+    def __call__(self, img, training=None, **kwargs):
+        """CCT.call(img, training=None) (cct.py:342-345).  img: NHWC numpy or torch of exactly the constructed img_size."""
+        if training:
+            raise NotImplementedError("CCT(training=True) needs dropout on the attention probabilities (rate 0.1, cct.py:132) and per-sample "
+                                      "stochastic depth (rates up to 0.1, cct.py:74-91,161,170); neither is built.  Only the deterministic path "
+                                      "(training falsy) is supported.")
+        x, proto = VitxModel._as_host(img)
+        if x.ndim != 4 or x.shape[3] != self.n_input_channels:
+            raise ValueError(f"expected NHWC images [b, H, W, {self.n_input_channels}]")
+        b, H, W, _c = x.shape
+        if (H, W) != self.img_size:
+            raise ValueError(f"CCT was built for img_size {self.img_size}; got images of {(H, W)} (the positional embedding and the sequence "
+                             "length belong to the constructed size)")
+        h = self._ensure_handle(b)
+        self._img_shape = (b, H, W, self.n_input_channels)
+        out = np.empty((b, self.num_classes), dtype=np.float32)
+        N.check(N.lib().vitx_cct_forward(h, x.ctypes.data_as(C.c_void_p), b, out.ctypes.data_as(C.c_void_p)))
+        return VitxModel._like(out, proto)
+
+    call = __call__
+    predict = lambda self, img, **kw: self(img, training=False, **kw)
+
+    def backward(self, dlogits, want_dimg: bool = False):
+        """VJP of the last forward.  Returns ({name: grad}, dimg | None)."""
+        if self._handle is None:
+            raise N.VitxError(N.ERR_STATE, "backward requires a preceding forward")
+        d, _ = VitxModel._as_host(dlogits)
+        dimg = np.empty(self._img_shape, dtype=np.float32) if want_dimg else None
+        N.check(N.lib().vitx_cct_backward(self._handle, d.ctypes.data_as(C.c_void_p), dimg.ctypes.data_as(C.c_void_p) if want_dimg else None))
+        g = np.empty(self._n, dtype=np.float32)
+        N.check(N.lib().vitx_cct_get_grads(self._handle, g.ctypes.data_as(C.c_void_p), self._n))
+        return {n: g[o:o + int(np.prod(s))].reshape(s) for n, s, o in self._table}, dimg
+
+    def read(self, which: str) -> np.ndarray:
+        """Tensors of the last forward for bisecting: 'tokens' / 'encoded' [b, n, dim], 'pool_weights' [b, n], 'pooled' [b, dim]."""
+        if self._handle is None:
+            raise N.VitxError(N.ERR_STATE, "read requires a preceding forward")
+        b = self._img_shape[0]
+        cap = b * self.sequence_length * self.embedding_dim
+        buf, n = np.empty(cap, dtype=np.float32), C.c_int64()
+        N.check(N.lib().vitx_cct_read(self._handle, which.encode(), buf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
+        out = buf[:n.value]
+        return out.reshape(b, -1, self.embedding_dim) if which in ("tokens", "encoded") else out.reshape(b, -1)
+
+    # ---- not provided for CCT: refuse instead of misbehaving
+    def comm_init(self, *a, **k):
+        raise NotImplementedError("CCT: data parallel is not supported (all-reduce grads_dev() outside the library)")
+
+    def optimizer_step(self, *a, **k):
+        raise NotImplementedError("CCT: no in-library optimizer step (update params_dev() outside the library, then params_changed())")
+
+    apply_gradients = optimizer_step
+
+    def capture_graph(self, *a, **k):
+        raise NotImplementedError("CCT: HIP graph capture is not supported")
