@@ -4,7 +4,7 @@
 #include <cstring>
 #include <map>
 
-#include "engine.h"
+#include "composite.h"
 
 static thread_local std::string g_last_error;
 
@@ -12,17 +12,7 @@ static int fail(int code, const std::string& msg) {
   g_last_error = msg;
   return code;
 }
-int capi_fail(int code, const std::string& msg) { return fail(code, msg); }   // shared with mim.hip
-#define CAPI_HIP(x)                                                                                    \
-  do {                                                                                                 \
-    hipError_t e_ = (x);                                                                               \
-    if (e_ != hipSuccess) return fail(VITX_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_));   \
-  } while (0)
-#define CAPI_TRY try {
-#define CAPI_CATCH                                                       \
-  }                                                                      \
-  catch (const std::exception& ex) { return fail(VITX_ERR_INVALID, ex.what()); } \
-  catch (...) { return fail(VITX_ERR_INVALID, "unknown C++ exception"); }
+int capi_fail(int code, const std::string& msg) { return fail(code, msg); }   // what composite.h's macros and helpers report through
 
 extern "C" {
 
@@ -52,16 +42,7 @@ int32_t vitx_param_table_entry(const vitx_config* cfg, int64_t index, char* name
   std::vector<ParamDesc> t;
   std::string err = build_param_table(c, t);
   if (!err.empty()) return fail(VITX_ERR_INVALID, err);
-  if (index < 0 || index >= (int64_t)t.size()) return fail(VITX_ERR_INVALID, "parameter index out of range");
-  const ParamDesc& p = t[(size_t)index];
-  if (name && name_cap > 0) {
-    std::strncpy(name, p.name.c_str(), (size_t)name_cap - 1);
-    name[name_cap - 1] = 0;
-  }
-  if (shape) for (int i = 0; i < 4; ++i) shape[i] = i < (int)p.shape.size() ? p.shape[(size_t)i] : 1;
-  if (rank) *rank = (int32_t)p.shape.size();
-  if (offset_elems) *offset_elems = p.offset;
-  return VITX_OK;
+  return write_table_entry(t, index, name, name_cap, shape, rank, offset_elems);
   CAPI_CATCH
 }
 

@@ -10,18 +10,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "engine.h"
-
-int capi_fail(int code, const std::string& msg);   // capi.hip
-
-#define HIPCHK(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) {                                                                         \
-      err = std::string(#x) + ": " + hipGetErrorString(e_);                                         \
-      return VITX_ERR_HIP;                                                                          \
-    }                                                                                               \
-  } while (0)
+#include "composite.h"
 
 namespace {
 
@@ -136,8 +125,6 @@ __global__ void cct_accum_kernel(float* __restrict__ dst, const float* __restric
   if (e < n) dst[e] = first ? src[e] : dst[e] + src[e];
 }
 
-inline unsigned grid256(int64_t n) { return (unsigned)std::max<int64_t>(1, ceil_div(n, 256)); }
-
 // a launch (or a group of launches) booked under a kernel class of the engine's profiler (vitx_cct_profile_begin / _end)
 struct CctProf {
   vitx_engine* e;
@@ -158,26 +145,6 @@ struct CctProf {
   }
 };
 
-bool al16(std::initializer_list<const void*> ps) {
-  for (const void* p : ps) if (p && ((uintptr_t)p & 15)) return false;
-  return true;
-}
-// Y[M, N] = X[M, K] W[K, N] (+ bias)
-void gemm_xw(const float* X, int64_t ldx, const float* W, const float* bias, float* Y, int M, int N, int K, int x3, hipStream_t s) {
-  GenericGemmArgs g;
-  g.A = X; g.B = W; g.M = M; g.N = N; g.K = K; g.sam = ldx; g.sak = 1; g.sbk = N; g.sbn = 1; g.x3 = x3;
-  EpiParams ep;
-  ep.out = Y; ep.ldo = N; ep.M = M; ep.N = N; ep.bias = bias; ep.vec_ok = (N % 4 == 0) && al16({Y, bias});
-  launch_gemm_generic(g, ep, EPI_STORE_F32, 0, 0, 0, s);
-}
-// dX[M, K] = dY[M, N] W[K, N]^T
-void gemm_dyw(const float* dY, const float* W, float* dX, int M, int N, int K, int x3, hipStream_t s) {
-  GenericGemmArgs g;
-  g.A = dY; g.B = W; g.M = M; g.N = K; g.K = N; g.sam = N; g.sak = 1; g.sbk = 1; g.sbn = N; g.x3 = x3;
-  EpiParams ep;
-  ep.out = dX; ep.ldo = K; ep.M = M; ep.N = K; ep.vec_ok = (K % 4 == 0) && al16({dX});
-  launch_gemm_generic(g, ep, EPI_STORE_F32, 0, 0, 0, s);
-}
 // Weight gradient of a convolution: dWp[Kp, N] = rows[M, Kp]^T dY[M, N] over all Kp (>= 64) padded columns.  On the split-operand kernel the M token
 // rows are cut into slices (the kernel's batch index, the last one shorter) so that tiles x slices fills the chip; the fp32 partials are summed in
 // slice order by launch_reduce_partials.  `part` holds max_slices * Kp * N floats.  The first K * N floats of dWp are the kernel's gradient.
@@ -186,7 +153,7 @@ void conv_wgrad(const float* rows, int Kp, const float* dY, float* dWp, float* p
   GenericGemmArgs g;
   g.A = rows; g.B = dY; g.M = Kp; g.N = N; g.K = M; g.sam = 1; g.sak = Kp; g.sbk = N; g.sbn = 1; g.x3 = x3;
   EpiParams ep;
-  ep.out = dWp; ep.ldo = N; ep.M = Kp; ep.N = N; ep.vec_ok = (N % 4 == 0) && al16({dWp, part});
+  ep.out = dWp; ep.ldo = N; ep.M = Kp; ep.N = N; ep.vec_ok = (N % 4 == 0) && aligned16({dWp, part});
   int slices = 1;
   if (x3 && gemm_bf16x3_supported(g, 0, 0, 0)) {
     const int64_t tiles = ceil_div(Kp, 128) * ceil_div(N, 128);
@@ -203,15 +170,6 @@ void conv_wgrad(const float* rows, int Kp, const float* dY, float* dWp, float* p
   launch_gemm_generic(g, ep, EPI_STORE_F32, 0, 0, 0, s);
   if (slices > 1) launch_reduce_partials(part, slices, (int64_t)Kp * N, (int64_t)Kp * N, dWp, 1.0f, s);
 }
-// dW[K, N] = X[M, K]^T dY[M, N]
-void gemm_xtdy(const float* X, int64_t ldx, const float* dY, float* dW, int M, int N, int K, int x3, hipStream_t s) {
-  GenericGemmArgs g;
-  g.A = X; g.B = dY; g.M = K; g.N = N; g.K = M; g.sam = 1; g.sak = ldx; g.sbk = N; g.sbn = 1; g.x3 = x3;
-  EpiParams ep;
-  ep.out = dW; ep.ldo = N; ep.M = K; ep.N = N; ep.vec_ok = (N % 4 == 0) && al16({dW});
-  launch_gemm_generic(g, ep, EPI_STORE_F32, 0, 0, 0, s);
-}
-
 // one conv layer of the tokenizer and the geometry of its two 'SAME' stages
 struct ConvLayer {
   int H = 0, W = 0, Cin = 0, Cout = 0;   // input extent / planes, filters
@@ -239,7 +197,7 @@ struct vitx_cct {
   int64_t pool_w = -1, pool_b = -1, pos = -1, norm_g = -1, norm_b = -1, fc_w = -1, fc_b = -1;
   int n = 0, d = 0, nc = 0, B = 0, x3 = 0;
   hipStream_t stream = nullptr;
-  std::vector<void*> allocs;
+  DevicePool pool;
   float *img = nullptr, *dimg = nullptr, *logits = nullptr, *dlogits = nullptr;
   float *rows = nullptr, *drows = nullptr, *gw_part = nullptr, *gw_slices = nullptr, *dconv = nullptr, *dact[2] = {nullptr, nullptr};
   float *sine = nullptr, *tok_in = nullptr, *enc = nullptr, *xn = nullptr, *mean = nullptr, *rstd = nullptr, *p = nullptr, *pooled = nullptr;
@@ -249,21 +207,6 @@ struct vitx_cct {
 };
 
 namespace {
-
-struct TableBuilder {
-  std::vector<ParamDesc>& t;
-  int64_t n = 0, na = 0;
-  int64_t add(const std::string& name, std::vector<int64_t> shape) {
-    ParamDesc p;
-    p.name = name; p.shape = shape; p.count = 1;
-    for (int64_t s : shape) p.count *= s;
-    p.offset = n; p.aoff = na;
-    n += p.count;
-    na += round_up(p.count, 4);
-    t.push_back(p);
-    return p.aoff;
-  }
-};
 
 // conv layers with their 'SAME' geometry (cct.py:190-200); "" or what is wrong with the configuration
 std::string cct_geometry(const vitx_cct_config& c, std::vector<ConvLayer>& out) {
@@ -325,7 +268,7 @@ std::string cct_param_table(const vitx_cct_config& c, std::vector<ParamDesc>& ou
     m->n = (int)n; m->d = (int)d; m->nc = c.num_classes;
   }
   if (n_elems) *n_elems = tb.n;
-  if (n_arena) *n_arena = tb.na;
+  if (n_arena) *n_arena = tb.n_arena;
   return "";
 }
 
@@ -361,25 +304,12 @@ int cct_check(const vitx_cct_config& c, std::string& err) {
   return VITX_OK;
 }
 
-int cct_alloc(vitx_cct* m, float** p, int64_t elems, std::string& err) {
-  const size_t bytes = (size_t)round_up(std::max<int64_t>(elems, 4) * 4, 256);
-  void* q = nullptr;
-  HIPCHK(hipMalloc(&q, bytes));
-  HIPCHK(hipMemsetAsync(q, 0, bytes, m->stream));
-  m->allocs.push_back(q);
-  *p = (float*)q;
-  return VITX_OK;
-}
-#define CALLOC(ptr, elems)                                     \
-  do {                                                         \
-    int rc_ = cct_alloc(m, &(ptr), (int64_t)(elems), err);     \
-    if (rc_ != VITX_OK) return fail(rc_);                      \
-  } while (0)
+#define CALLOC(ptr, elems) POOL_ALLOC(m->pool, ptr, (int64_t)(elems) * 4, m->stream, fail(rc_))
 
 void cct_destroy(vitx_cct* m) {
   if (!m) return;
   (void)hipDeviceSynchronize();
-  for (void* p : m->allocs) (void)hipFree(p);
+  m->pool.free_all();
   if (m->eng) engine_destroy(m->eng);
   delete m;
 }
@@ -486,7 +416,7 @@ int cct_forward(vitx_cct* m, const float* img_dev, int b, std::string& err) {
       const int nb = std::min(L.chunk, b - b0);
       { CctProf pr(m->eng, "cct_im2col"); launch_cct_im2col(x + b0 * in_img, m->rows, nb, L.H, L.W, L.Cin, c.kernel_size, c.stride, L.Kp, s); }
       CctProf pr(m->eng, "cct_conv_gemm");
-      gemm_xw(m->rows, L.Kp, P + L.w, nullptr, L.conv + b0 * out_img, nb * L.oh * L.ow, L.Cout, L.K, m->x3, s);
+      dense_fwd(m->rows, L.Kp, P + L.w, nullptr, L.conv + b0 * out_img, nb * L.oh * L.ow, L.Cout, L.K, s, m->x3);
     }
     CctProf pr(m->eng, "cct_relu_maxpool_fwd");
     launch_cct_relu_maxpool_fwd(L.conv, L.pooled, b, L.oh, L.ow, L.Cout, c.pooling_kernel_size, c.pooling_stride, s);
@@ -508,7 +438,7 @@ int cct_forward(vitx_cct* m, const float* img_dev, int b, std::string& err) {
     hipLaunchKernelGGL(cct_seqpool_fwd_kernel, dim3((unsigned)b), dim3(SP_THREADS), seqpool_lds_bytes(n, false), s, m->xn, P + m->pool_w, P + m->pool_b,
                        m->p, m->pooled, n, d);                                                                                       // :293-299
   }
-  gemm_xw(m->pooled, d, P + m->fc_w, P + m->fc_b, m->logits, b, m->nc, d, 0, s);                                                    // :303
+  dense_fwd(m->pooled, d, P + m->fc_w, P + m->fc_b, m->logits, b, m->nc, d, s);                                                    // :303
   m->have_fwd = true;
   return VITX_OK;
 }
@@ -524,9 +454,9 @@ int cct_backward(vitx_cct* m, const float* dlogits_dev, float* dimg_dev, std::st
   const int b = m->b, n = m->n, d = m->d;
   launch_fill_zero(G, m->n_arena * 4, s);
   // fc
-  gemm_xtdy(m->pooled, d, dlogits_dev, G + m->fc_w, b, m->nc, d, 0, s);
+  dense_dw(m->pooled, d, dlogits_dev, G + m->fc_w, b, m->nc, d, s);
   launch_colsum(dlogits_dev, 0, m->nc, b, m->nc, m->ws, G + m->fc_b, s);
-  gemm_dyw(dlogits_dev, P + m->fc_w, m->dpooled, b, m->nc, d, 0, s);
+  dense_dx(dlogits_dev, P + m->fc_w, m->dpooled, b, m->nc, d, s);
   // sequence pooling: per-image partials, then a fixed-order sum over the images
   {
     CctProf pr(m->eng, "cct_seqpool_bwd");
@@ -564,7 +494,7 @@ int cct_backward(vitx_cct* m, const float* dlogits_dev, float* dimg_dev, std::st
         conv_wgrad(m->rows, L.Kp, dy, m->gw_part, m->gw_slices, rows, L.Cout, m->x3, s);
         const int64_t nw = (int64_t)L.K * L.Cout;
         hipLaunchKernelGGL(cct_accum_kernel, dim3(grid256(nw)), dim3(256), 0, s, G + L.w, (const float*)m->gw_part, nw, b0 == 0 ? 1 : 0);
-        if (dxin) gemm_dyw(dy, P + L.w, m->drows, rows, L.Cout, L.K, m->x3, s);
+        if (dxin) dense_dx(dy, P + L.w, m->drows, rows, L.Cout, L.K, s, m->x3);
       }
       if (dxin) {
         CctProf pr(m->eng, "cct_col2im");
@@ -578,21 +508,10 @@ int cct_backward(vitx_cct* m, const float* dlogits_dev, float* dimg_dev, std::st
 
 }  // namespace
 
-#define X_TRY try {
-#define X_CATCH                                                                       \
-  }                                                                                   \
-  catch (const std::exception& ex) { return capi_fail(VITX_ERR_INVALID, ex.what()); } \
-  catch (...) { return capi_fail(VITX_ERR_INVALID, "unknown C++ exception"); }
-#define X_HIP(x)                                                                                           \
-  do {                                                                                                     \
-    hipError_t e_ = (x);                                                                                   \
-    if (e_ != hipSuccess) return capi_fail(VITX_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_));  \
-  } while (0)
-
 extern "C" {
 
 int32_t vitx_cct_param_table_size(const vitx_cct_config* cfg, int64_t* n_tensors, int64_t* n_elems) {
-  X_TRY
+  CAPI_TRY
   if (!cfg) return capi_fail(VITX_ERR_INVALID, "null argument");
   std::vector<ParamDesc> t;
   int64_t n = 0;
@@ -601,36 +520,30 @@ int32_t vitx_cct_param_table_size(const vitx_cct_config* cfg, int64_t* n_tensors
   if (n_tensors) *n_tensors = (int64_t)t.size();
   if (n_elems) *n_elems = n;
   return VITX_OK;
-  X_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_cct_param_table_entry(const vitx_cct_config* cfg, int64_t index, char* name, int32_t name_cap, int64_t shape[4], int32_t* rank,
                                    int64_t* offset_elems) {
-  X_TRY
+  CAPI_TRY
   if (!cfg) return capi_fail(VITX_ERR_INVALID, "null argument");
   std::vector<ParamDesc> t;
   std::string e = cct_param_table(*cfg, t, nullptr, nullptr);
   if (!e.empty()) return capi_fail(VITX_ERR_INVALID, e);
-  if (index < 0 || index >= (int64_t)t.size()) return capi_fail(VITX_ERR_INVALID, "parameter index out of range");
-  const ParamDesc& p = t[(size_t)index];
-  if (name && name_cap > 0) { std::strncpy(name, p.name.c_str(), (size_t)name_cap - 1); name[name_cap - 1] = 0; }
-  if (shape) for (int i = 0; i < 4; ++i) shape[i] = i < (int)p.shape.size() ? p.shape[(size_t)i] : 1;
-  if (rank) *rank = (int32_t)p.shape.size();
-  if (offset_elems) *offset_elems = p.offset;
-  return VITX_OK;
-  X_CATCH
+  return write_table_entry(t, index, name, name_cap, shape, rank, offset_elems);
+  CAPI_CATCH
 }
 int32_t vitx_cct_sequence_length(const vitx_cct_config* cfg, int32_t* n_tokens) {
-  X_TRY
+  CAPI_TRY
   if (!cfg || !n_tokens) return capi_fail(VITX_ERR_INVALID, "null argument");
   std::vector<ConvLayer> conv;
   std::string e = cct_geometry(*cfg, conv);
   if (!e.empty()) return capi_fail(VITX_ERR_INVALID, e);
   *n_tokens = conv.back().ph * conv.back().pw;
   return VITX_OK;
-  X_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_cct_create(const vitx_cct_config* cfg, vitx_cct_handle* out) {
-  X_TRY
+  CAPI_TRY
   if (!cfg || !out) return capi_fail(VITX_ERR_INVALID, "null argument");
   std::string err;
   vitx_cct* m = nullptr;
@@ -638,117 +551,65 @@ int32_t vitx_cct_create(const vitx_cct_config* cfg, vitx_cct_handle* out) {
   if (rc != VITX_OK) return capi_fail(rc, err);
   *out = m;
   return VITX_OK;
-  X_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_cct_destroy(vitx_cct_handle m) {
-  X_TRY
+  CAPI_TRY
   cct_destroy(m);
   return VITX_OK;
-  X_CATCH
+  CAPI_CATCH
 }
-static int cct_copy_blob(vitx_cct* m, float* arena, float* host, int64_t n, bool to_device) {
-  if (n != m->n_params) return capi_fail(VITX_ERR_INVALID, "blob size does not match the CCT parameter table");
-  for (auto& p : m->table) {
-    if (to_device) X_HIP(hipMemcpyAsync(arena + p.aoff, host + p.offset, (size_t)p.count * 4, hipMemcpyHostToDevice, m->stream));
-    else X_HIP(hipMemcpyAsync(host + p.offset, arena + p.aoff, (size_t)p.count * 4, hipMemcpyDeviceToHost, m->stream));
-  }
-  X_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
-}
-int32_t vitx_cct_set_params(vitx_cct_handle m, const float* host_blob, int64_t n) {
-  X_TRY
-  if (!m || !host_blob) return capi_fail(VITX_ERR_INVALID, "null argument");
-  int rc = cct_copy_blob(m, m->params, const_cast<float*>(host_blob), n, true);
-  if (rc != VITX_OK) return rc;
-  std::string err;
-  if ((rc = push_params(m, err)) != VITX_OK) return capi_fail(rc, err);
-  X_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
-  X_CATCH
-}
-int32_t vitx_cct_get_params(vitx_cct_handle m, float* host_blob, int64_t n) {
-  X_TRY
-  if (!m || !host_blob) return capi_fail(VITX_ERR_INVALID, "null argument");
-  return cct_copy_blob(m, m->params, host_blob, n, false);
-  X_CATCH
-}
-int32_t vitx_cct_get_grads(vitx_cct_handle m, float* host_blob, int64_t n) {
-  X_TRY
-  if (!m || !host_blob) return capi_fail(VITX_ERR_INVALID, "null argument");
-  return cct_copy_blob(m, m->grads, host_blob, n, false);
-  X_CATCH
-}
-int32_t vitx_cct_params_dev(vitx_cct_handle m, float** dev_ptr, int64_t* n_elems) {
-  if (!m || !dev_ptr) return capi_fail(VITX_ERR_INVALID, "null argument");
-  *dev_ptr = m->params;
-  if (n_elems) *n_elems = m->n_arena;
-  return VITX_OK;
-}
-int32_t vitx_cct_grads_dev(vitx_cct_handle m, float** dev_ptr, int64_t* n_elems) {
-  if (!m || !dev_ptr) return capi_fail(VITX_ERR_INVALID, "null argument");
-  *dev_ptr = m->grads;
-  if (n_elems) *n_elems = m->n_arena;
-  return VITX_OK;
-}
-int32_t vitx_cct_params_changed(vitx_cct_handle m) {
-  X_TRY
-  if (!m) return capi_fail(VITX_ERR_INVALID, "null handle");
-  std::string err;
-  int rc = push_params(m, err);
-  if (rc != VITX_OK) return capi_fail(rc, err);
-  return VITX_OK;
-  X_CATCH
-}
+COMPOSITE_ARENA_EXPORTS(vitx_cct, "blob size does not match the CCT parameter table")
 int32_t vitx_cct_forward_dev(vitx_cct_handle m, const float* img_dev, int32_t b, float* logits_dev_or_null) {
-  X_TRY
+  CAPI_TRY
   if (!m || !img_dev) return capi_fail(VITX_ERR_INVALID, "null argument");
   if (b <= 0 || b > m->cfg.max_batch) return capi_fail(VITX_ERR_INVALID, "batch must be in [1, max_batch]");
   // the tokenizer's VJP re-reads the image: the handle keeps its own copy
   if (img_dev != m->img)
-    X_HIP(hipMemcpyAsync(m->img, img_dev, (size_t)b * m->cfg.img_height * m->cfg.img_width * m->cfg.n_input_channels * 4, hipMemcpyDeviceToDevice, m->stream));
+    CAPI_HIP(hipMemcpyAsync(m->img, img_dev, (size_t)b * m->cfg.img_height * m->cfg.img_width * m->cfg.n_input_channels * 4, hipMemcpyDeviceToDevice, m->stream));
   std::string err;
   int rc = cct_forward(m, m->img, b, err);
   if (rc != VITX_OK) return capi_fail(rc, err);
-  if (logits_dev_or_null) X_HIP(hipMemcpyAsync(logits_dev_or_null, m->logits, (size_t)b * m->nc * 4, hipMemcpyDeviceToDevice, m->stream));
+  if (logits_dev_or_null) CAPI_HIP(hipMemcpyAsync(logits_dev_or_null, m->logits, (size_t)b * m->nc * 4, hipMemcpyDeviceToDevice, m->stream));
   return VITX_OK;
-  X_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_cct_forward(vitx_cct_handle m, const float* img_host, int32_t b, float* logits_host) {
-  X_TRY
+  CAPI_TRY
   if (!m || !img_host || !logits_host) return capi_fail(VITX_ERR_INVALID, "null argument");
   if (b <= 0 || b > m->cfg.max_batch) return capi_fail(VITX_ERR_INVALID, "batch must be in [1, max_batch]");
-  X_HIP(hipMemcpyAsync(m->img, img_host, (size_t)b * m->cfg.img_height * m->cfg.img_width * m->cfg.n_input_channels * 4, hipMemcpyHostToDevice, m->stream));
+  CAPI_HIP(hipMemcpyAsync(m->img, img_host, (size_t)b * m->cfg.img_height * m->cfg.img_width * m->cfg.n_input_channels * 4, hipMemcpyHostToDevice, m->stream));
   std::string err;
   int rc = cct_forward(m, m->img, b, err);
   if (rc != VITX_OK) return capi_fail(rc, err);
-  X_HIP(hipMemcpyAsync(logits_host, m->logits, (size_t)b * m->nc * 4, hipMemcpyDeviceToHost, m->stream));
-  X_HIP(hipStreamSynchronize(m->stream));
+  CAPI_HIP(hipMemcpyAsync(logits_host, m->logits, (size_t)b * m->nc * 4, hipMemcpyDeviceToHost, m->stream));
+  CAPI_HIP(hipStreamSynchronize(m->stream));
   return VITX_OK;
-  X_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_cct_backward_dev(vitx_cct_handle m, const float* dlogits_dev, float* dimg_dev_or_null) {
-  X_TRY
+  CAPI_TRY
   if (!m || !dlogits_dev) return capi_fail(VITX_ERR_INVALID, "null argument");
   std::string err;
   int rc = cct_backward(m, dlogits_dev, dimg_dev_or_null, err);
   if (rc != VITX_OK) return capi_fail(rc, err);
   return VITX_OK;
-  X_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_cct_backward(vitx_cct_handle m, const float* dlogits_host, float* dimg_host_or_null) {
-  X_TRY
+  CAPI_TRY
   if (!m || !dlogits_host) return capi_fail(VITX_ERR_INVALID, "null argument");
   if (!m->have_fwd) return capi_fail(VITX_ERR_STATE, "backward requires a preceding forward");
-  X_HIP(hipMemcpyAsync(m->dlogits, dlogits_host, (size_t)m->b * m->nc * 4, hipMemcpyHostToDevice, m->stream));
+  CAPI_HIP(hipMemcpyAsync(m->dlogits, dlogits_host, (size_t)m->b * m->nc * 4, hipMemcpyHostToDevice, m->stream));
   std::string err;
   int rc = cct_backward(m, m->dlogits, dimg_host_or_null ? m->dimg : nullptr, err);
   if (rc != VITX_OK) return capi_fail(rc, err);
   if (dimg_host_or_null)
-    X_HIP(hipMemcpyAsync(dimg_host_or_null, m->dimg, (size_t)m->b * m->cfg.img_height * m->cfg.img_width * m->cfg.n_input_channels * 4, hipMemcpyDeviceToHost,
+    CAPI_HIP(hipMemcpyAsync(dimg_host_or_null, m->dimg, (size_t)m->b * m->cfg.img_height * m->cfg.img_width * m->cfg.n_input_channels * 4, hipMemcpyDeviceToHost,
                          m->stream));
-  X_HIP(hipStreamSynchronize(m->stream));
+  CAPI_HIP(hipStreamSynchronize(m->stream));
   return VITX_OK;
-  X_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_cct_profile_begin(vitx_cct_handle m) {
   if (!m) return capi_fail(VITX_ERR_INVALID, "null handle");
@@ -759,7 +620,7 @@ int32_t vitx_cct_profile_end(vitx_cct_handle m, vitx_kernel_stat* out, int32_t c
   return vitx_profile_end(m->eng, out, cap, n_out);
 }
 int32_t vitx_cct_read(vitx_cct_handle m, const char* which, float* out_host, int64_t cap, int64_t* n_elems) {
-  X_TRY
+  CAPI_TRY
   if (!m || !which || !out_host) return capi_fail(VITX_ERR_INVALID, "null argument");
   if (!m->have_fwd) return capi_fail(VITX_ERR_STATE, "read requires a preceding forward");
   const std::string w = which;
@@ -772,10 +633,10 @@ int32_t vitx_cct_read(vitx_cct_handle m, const char* which, float* out_host, int
   else return capi_fail(VITX_ERR_INVALID, "unknown tensor name");
   if (n_elems) *n_elems = n;
   if (n > cap) return capi_fail(VITX_ERR_INVALID, "output buffer too small");
-  X_HIP(hipMemcpyAsync(out_host, src, (size_t)n * 4, hipMemcpyDeviceToHost, m->stream));
-  X_HIP(hipStreamSynchronize(m->stream));
+  CAPI_HIP(hipMemcpyAsync(out_host, src, (size_t)n * 4, hipMemcpyDeviceToHost, m->stream));
+  CAPI_HIP(hipStreamSynchronize(m->stream));
   return VITX_OK;
-  X_CATCH
+  CAPI_CATCH
 }
 
 }  // extern "C"

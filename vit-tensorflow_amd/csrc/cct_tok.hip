@@ -7,11 +7,9 @@
 // holds at least one tap inside it.
 #include <algorithm>
 
-#include "kernels.h"
+#include "composite.h"
 
 namespace {
-
-inline unsigned grid256(int64_t n) { return (unsigned)std::max<int64_t>(1, ceil_div(n, 256)); }
 
 template <int V> struct VecT;
 template <> struct VecT<1> { using type = float; };

@@ -7,18 +7,7 @@
 #include <algorithm>
 #include <cstring>
 
-#include "engine.h"
-
-int capi_fail(int code, const std::string& msg);   // capi.hip
-
-#define HIPCHK(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) {                                                                         \
-      err = std::string(#x) + ": " + hipGetErrorString(e_);                                         \
-      return VITX_ERR_HIP;                                                                          \
-    }                                                                                               \
-  } while (0)
+#include "composite.h"
 
 namespace {
 
@@ -209,37 +198,6 @@ __global__ void crossvit_add_kernel(const float* __restrict__ a, const float* __
   if (e < n) out[e] = a[e] + b[e];
 }
 
-inline unsigned grid256(int64_t n) { return (unsigned)std::max<int64_t>(1, ceil_div(n, 256)); }
-
-bool al16(std::initializer_list<const void*> ps) {
-  for (const void* p : ps) if (p && ((uintptr_t)p & 15)) return false;
-  return true;
-}
-// Y[M, N] = X[M, K] W[K, N] (+ bias)
-void gemm_xw(const float* X, int64_t ldx, const float* W, const float* bias, float* Y, int M, int N, int K, hipStream_t s) {
-  GenericGemmArgs g;
-  g.A = X; g.B = W; g.M = M; g.N = N; g.K = K; g.sam = ldx; g.sak = 1; g.sbk = N; g.sbn = 1;
-  EpiParams ep;
-  ep.out = Y; ep.ldo = N; ep.M = M; ep.N = N; ep.bias = bias; ep.vec_ok = (N % 4 == 0) && al16({Y, bias});
-  launch_gemm_generic(g, ep, EPI_STORE_F32, 0, 0, 0, s);
-}
-// dX[M, K] = dY[M, N] W[K, N]^T
-void gemm_dyw(const float* dY, const float* W, float* dX, int M, int N, int K, hipStream_t s) {
-  GenericGemmArgs g;
-  g.A = dY; g.B = W; g.M = M; g.N = K; g.K = N; g.sam = N; g.sak = 1; g.sbk = 1; g.sbn = N;
-  EpiParams ep;
-  ep.out = dX; ep.ldo = K; ep.M = M; ep.N = K; ep.vec_ok = (K % 4 == 0) && al16({dX});
-  launch_gemm_generic(g, ep, EPI_STORE_F32, 0, 0, 0, s);
-}
-// dW[K, N] = X[M, K]^T dY[M, N]
-void gemm_xtdy(const float* X, int64_t ldx, const float* dY, float* dW, int M, int N, int K, hipStream_t s) {
-  GenericGemmArgs g;
-  g.A = X; g.B = dY; g.M = K; g.N = N; g.K = M; g.sam = 1; g.sak = ldx; g.sbk = N; g.sbn = 1;
-  EpiParams ep;
-  ep.out = dW; ep.ldo = N; ep.M = K; ep.N = N; ep.vec_ok = (N % 4 == 0) && al16({dW});
-  launch_gemm_generic(g, ep, EPI_STORE_F32, 0, 0, 0, s);
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ composite
@@ -271,7 +229,7 @@ struct vitx_crossvit {
   int dim[2] = {0, 0}, np_max[2] = {0, 0}, patch[2] = {0, 0};
   int ci = 0, ch = 0, cdh = 0, nc = 0, B = 0;
   hipStream_t stream = nullptr;
-  std::vector<void*> allocs;
+  DevicePool pool;
   // per branch
   float* tok0[2] = {};                // embedding output (after emb_dropout)
   std::vector<float*> E[2], T[2], fmean[2], frstd[2];   // per layer: encoder output, final-norm output (cls row updated in place by the cross layers)
@@ -293,21 +251,6 @@ uint64_t mix_seed(uint64_t seed, uint64_t k) {   // splitmix64 step: independent
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
-
-struct TableBuilder {
-  std::vector<ParamDesc>& t;
-  int64_t n = 0, na = 0;
-  int64_t add(const std::string& name, std::vector<int64_t> shape) {
-    ParamDesc p;
-    p.name = name; p.shape = shape; p.count = 1;
-    for (int64_t s : shape) p.count *= s;
-    p.offset = n; p.aoff = na;
-    n += p.count;
-    na += round_up(p.count, 4);
-    t.push_back(p);
-    return p.aoff;
-  }
-};
 
 }  // namespace
 
@@ -374,26 +317,13 @@ std::string crossvit_param_table(const vitx_crossvit_config& c, std::vector<Para
     tb.add(p + "kernel", {dm[br], c.num_classes}); tb.add(p + "bias", {c.num_classes});
   }
   if (n_elems) *n_elems = tb.n;
-  if (n_arena) *n_arena = tb.na;
+  if (n_arena) *n_arena = tb.n_arena;
   return "";
 }
 
 namespace {
 
-int xv_alloc(vitx_crossvit* m, float** p, int64_t elems, std::string& err) {
-  const size_t bytes = (size_t)round_up(std::max<int64_t>(elems, 4) * 4, 256);
-  void* q = nullptr;
-  HIPCHK(hipMalloc(&q, bytes));
-  HIPCHK(hipMemsetAsync(q, 0, bytes, m->stream));
-  m->allocs.push_back(q);
-  *p = (float*)q;
-  return VITX_OK;
-}
-#define XALLOC(ptr, elems)                                    \
-  do {                                                        \
-    int rc_ = xv_alloc(m, &(ptr), (int64_t)(elems), err);     \
-    if (rc_ != VITX_OK) return rc_;                           \
-  } while (0)
+#define XALLOC(ptr, elems) POOL_ALLOC(m->pool, ptr, (int64_t)(elems) * 4, m->stream, rc_)
 
 const ParamDesc* find_param(const vitx_engine* e, const std::string& name) {
   for (const auto& p : e->table)
@@ -404,7 +334,7 @@ const ParamDesc* find_param(const vitx_engine* e, const std::string& name) {
 void crossvit_destroy(vitx_crossvit* m) {
   if (!m) return;
   (void)hipDeviceSynchronize();
-  for (void* p : m->allocs) (void)hipFree(p);
+  m->pool.free_all();
   for (auto* e : m->eng) engine_destroy(e);
   delete m;
 }
@@ -575,17 +505,17 @@ void cross_forward(vitx_crossvit* m, XLayer& x, float* X, int nx, const float* Y
   const int b = m->b, ci = m->ci;
   const float* P = m->params;
   hipLaunchKernelGGL(crossvit_cls_gather_kernel, dim3(grid256((int64_t)b * x.dx)), dim3(256), 0, s, X, nx, x.dx, b, x.x0);
-  if (x.proj) gemm_xw(x.x0, x.dx, P + x.pin.w, P + x.pin.b, x.xin, b, x.D, x.dx, s);                          // project_in  :133-134
+  if (x.proj) dense_fwd(x.x0, x.dx, P + x.pin.w, P + x.pin.b, x.xin, b, x.D, x.dx, s);                          // project_in  :133-134
   launch_layernorm_fwd(x.xin, x.D, P + x.ln_g, P + x.ln_b, x.xn, 0, x.D, x.mean, x.rstd, b, x.D, m->cfg.ln_eps, s);   // PreNorm :22
-  gemm_xw(x.xn, x.D, P + x.q.w, nullptr, x.q_act, b, ci, x.D, s);                                             // to_q     :78
+  dense_fwd(x.xn, x.D, P + x.q.w, nullptr, x.q_act, b, ci, x.D, s);                                             // to_q     :78
   const int64_t nrow = (int64_t)b * ny;
   hipLaunchKernelGGL(crossvit_ctx_assemble_kernel, dim3(grid256(nrow * x.D)), dim3(256), 0, s, x.xn, Y, ny, x.D, b, m->ctx);   // :75-76
-  gemm_xw(m->ctx, x.D, P + x.kv.w, nullptr, x.kv_act, (int)nrow, 2 * ci, x.D, s);                             // to_kv    :79
+  dense_fwd(m->ctx, x.D, P + x.kv.w, nullptr, x.kv_act, (int)nrow, 2 * ci, x.D, s);                             // to_kv    :79
   launch_xattn_fwd(x.q_act, x.kv_act, x.o, x.lse, b, ny, m->ch, m->cdh, s);                                   // :80-88
-  gemm_xw(x.o, ci, P + x.out.w, P + x.out.b, x.fd, b, x.D, ci, s);                                            // to_out   :89
+  dense_fwd(x.o, ci, P + x.out.w, P + x.out.b, x.fd, b, x.D, ci, s);                                            // to_out   :89
   if (m->training) launch_dropout(x.fd, 0, (int64_t)b * x.D, m->cfg.dropout, m->seed, site, s);
   const float* r = x.fd;
-  if (x.proj) { gemm_xw(x.fd, x.D, P + x.pout.w, P + x.pout.b, m->s_out, b, x.dx, x.D, s); r = m->s_out; }   // project_out :139-140
+  if (x.proj) { dense_fwd(x.fd, x.D, P + x.pout.w, P + x.pout.b, m->s_out, b, x.dx, x.D, s); r = m->s_out; }   // project_out :139-140
   hipLaunchKernelGGL(crossvit_cls_store_kernel, dim3(grid256((int64_t)b * x.dx)), dim3(256), 0, s, X, nx, x.dx, b, r, (const float*)nullptr, 1);
 }
 
@@ -599,31 +529,31 @@ void cross_backward(vitx_crossvit* m, XLayer& x, float* dX, int nx, const float*
   hipLaunchKernelGGL(crossvit_cls_gather_kernel, dim3(grid256((int64_t)b * x.dx)), dim3(256), 0, s, dX, nx, x.dx, b, dout);
   float* df = m->s_df;
   if (x.proj) {
-    gemm_dyw(dout, P + x.pout.w, df, b, x.dx, x.D, s);
-    gemm_xtdy(x.fd, x.D, dout, Gd + x.pout.w, b, x.dx, x.D, s);
+    dense_dx(dout, P + x.pout.w, df, b, x.dx, x.D, s);
+    dense_dw(x.fd, x.D, dout, Gd + x.pout.w, b, x.dx, x.D, s);
     launch_colsum(dout, 0, x.dx, b, x.dx, m->ws, Gd + x.pout.b, s);
   } else {
     (void)hipMemcpyAsync(df, dout, (size_t)b * x.D * 4, hipMemcpyDeviceToDevice, s);
   }
   if (m->training) launch_dropout(df, 0, (int64_t)b * x.D, m->cfg.dropout, m->seed, site, s);   // the forward's mask, replayed
-  gemm_xtdy(x.o, ci, df, Gd + x.out.w, b, x.D, ci, s);
+  dense_dw(x.o, ci, df, Gd + x.out.w, b, x.D, ci, s);
   launch_colsum(df, 0, x.D, b, x.D, m->ws, Gd + x.out.b, s);
-  gemm_dyw(df, P + x.out.w, m->s_do, b, x.D, ci, s);
+  dense_dx(df, P + x.out.w, m->s_do, b, x.D, ci, s);
   launch_xattn_bwd(x.q_act, x.kv_act, m->s_do, x.lse, m->s_dq, m->dkv, b, ny, m->ch, m->cdh, s);
-  gemm_xtdy(x.xn, x.D, m->s_dq, Gd + x.q.w, b, ci, x.D, s);
-  gemm_dyw(m->s_dq, P + x.q.w, m->s_dxn, b, ci, x.D, s);
+  dense_dw(x.xn, x.D, m->s_dq, Gd + x.q.w, b, ci, x.D, s);
+  dense_dx(m->s_dq, P + x.q.w, m->s_dxn, b, ci, x.D, s);
   const int64_t nrow = (int64_t)b * ny;
   hipLaunchKernelGGL(crossvit_ctx_assemble_kernel, dim3(grid256(nrow * x.D)), dim3(256), 0, s, x.xn, Y, ny, x.D, b, m->ctx);
-  gemm_xtdy(m->ctx, x.D, m->dkv, Gd + x.kv.w, (int)nrow, 2 * ci, x.D, s);
-  gemm_dyw(m->dkv, P + x.kv.w, m->dctx, (int)nrow, 2 * ci, x.D, s);
+  dense_dw(m->ctx, x.D, m->dkv, Gd + x.kv.w, (int)nrow, 2 * ci, x.D, s);
+  dense_dx(m->dkv, P + x.kv.w, m->dctx, (int)nrow, 2 * ci, x.D, s);
   hipLaunchKernelGGL(crossvit_ctx_split_bwd_kernel, dim3(grid256(nrow * x.D)), dim3(256), 0, s, m->dctx, ny, x.D, b, m->s_dxn, dY);
   launch_layernorm_bwd(m->s_dxn, 0, x.D, x.xin, x.D, x.mean, x.rstd, P + x.ln_g, nullptr, 0, m->s_dxin, x.D, nullptr, 0, m->ws, Gd + x.ln_g,
                        Gd + x.ln_b, nullptr, b, x.D, s);
   const float* dx0 = m->s_dxin;
   if (x.proj) {
-    gemm_xtdy(x.x0, x.dx, m->s_dxin, Gd + x.pin.w, b, x.D, x.dx, s);
+    dense_dw(x.x0, x.dx, m->s_dxin, Gd + x.pin.w, b, x.D, x.dx, s);
     launch_colsum(m->s_dxin, 0, x.D, b, x.D, m->ws, Gd + x.pin.b, s);
-    gemm_dyw(m->s_dxin, P + x.pin.w, m->s_dfd, b, x.D, x.dx, s);
+    dense_dx(m->s_dxin, P + x.pin.w, m->s_dfd, b, x.D, x.dx, s);
     dx0 = m->s_dfd;
   }
   // d(old cls) = residual + branch
@@ -719,21 +649,10 @@ int crossvit_backward(vitx_crossvit* m, const float* dlogits_dev, float* dimg_de
 
 }  // namespace
 
-#define X_TRY try {
-#define X_CATCH                                                                       \
-  }                                                                                   \
-  catch (const std::exception& ex) { return capi_fail(VITX_ERR_INVALID, ex.what()); } \
-  catch (...) { return capi_fail(VITX_ERR_INVALID, "unknown C++ exception"); }
-#define X_HIP(x)                                                                                           \
-  do {                                                                                                     \
-    hipError_t e_ = (x);                                                                                   \
-    if (e_ != hipSuccess) return capi_fail(VITX_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_));  \
-  } while (0)
-
 extern "C" {
 
 int32_t vitx_crossvit_param_table_size(const vitx_crossvit_config* cfg, int64_t* n_tensors, int64_t* n_elems) {
-  X_TRY
+  CAPI_TRY
   if (!cfg) return capi_fail(VITX_ERR_INVALID, "null argument");
   std::vector<ParamDesc> t;
   int64_t n = 0;
@@ -742,26 +661,20 @@ int32_t vitx_crossvit_param_table_size(const vitx_crossvit_config* cfg, int64_t*
   if (n_tensors) *n_tensors = (int64_t)t.size();
   if (n_elems) *n_elems = n;
   return VITX_OK;
-  X_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_crossvit_param_table_entry(const vitx_crossvit_config* cfg, int64_t index, char* name, int32_t name_cap, int64_t shape[4], int32_t* rank,
                                         int64_t* offset_elems) {
-  X_TRY
+  CAPI_TRY
   if (!cfg) return capi_fail(VITX_ERR_INVALID, "null argument");
   std::vector<ParamDesc> t;
   std::string e = crossvit_param_table(*cfg, t, nullptr, nullptr);
   if (!e.empty()) return capi_fail(VITX_ERR_INVALID, e);
-  if (index < 0 || index >= (int64_t)t.size()) return capi_fail(VITX_ERR_INVALID, "parameter index out of range");
-  const ParamDesc& p = t[(size_t)index];
-  if (name && name_cap > 0) { std::strncpy(name, p.name.c_str(), (size_t)name_cap - 1); name[name_cap - 1] = 0; }
-  if (shape) for (int i = 0; i < 4; ++i) shape[i] = i < (int)p.shape.size() ? p.shape[(size_t)i] : 1;
-  if (rank) *rank = (int32_t)p.shape.size();
-  if (offset_elems) *offset_elems = p.offset;
-  return VITX_OK;
-  X_CATCH
+  return write_table_entry(t, index, name, name_cap, shape, rank, offset_elems);
+  CAPI_CATCH
 }
 int32_t vitx_crossvit_create(const vitx_crossvit_config* cfg, vitx_crossvit_handle* out) {
-  X_TRY
+  CAPI_TRY
   if (!cfg || !out) return capi_fail(VITX_ERR_INVALID, "null argument");
   std::string err;
   vitx_crossvit* m = nullptr;
@@ -769,119 +682,67 @@ int32_t vitx_crossvit_create(const vitx_crossvit_config* cfg, vitx_crossvit_hand
   if (rc != VITX_OK) return capi_fail(rc, err);
   *out = m;
   return VITX_OK;
-  X_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_crossvit_destroy(vitx_crossvit_handle m) {
-  X_TRY
+  CAPI_TRY
   crossvit_destroy(m);
   return VITX_OK;
-  X_CATCH
+  CAPI_CATCH
 }
-static int xv_copy_blob(vitx_crossvit* m, float* arena, float* host, int64_t n, bool to_device) {
-  if (n != m->n_params) return capi_fail(VITX_ERR_INVALID, "blob size does not match the CrossViT parameter table");
-  for (auto& p : m->table) {
-    if (to_device) X_HIP(hipMemcpyAsync(arena + p.aoff, host + p.offset, (size_t)p.count * 4, hipMemcpyHostToDevice, m->stream));
-    else X_HIP(hipMemcpyAsync(host + p.offset, arena + p.aoff, (size_t)p.count * 4, hipMemcpyDeviceToHost, m->stream));
-  }
-  X_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
-}
-int32_t vitx_crossvit_set_params(vitx_crossvit_handle m, const float* host_blob, int64_t n) {
-  X_TRY
-  if (!m || !host_blob) return capi_fail(VITX_ERR_INVALID, "null argument");
-  int rc = xv_copy_blob(m, m->params, const_cast<float*>(host_blob), n, true);
-  if (rc != VITX_OK) return rc;
-  std::string err;
-  if ((rc = push_params(m, err)) != VITX_OK) return capi_fail(rc, err);
-  X_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
-  X_CATCH
-}
-int32_t vitx_crossvit_get_params(vitx_crossvit_handle m, float* host_blob, int64_t n) {
-  X_TRY
-  if (!m || !host_blob) return capi_fail(VITX_ERR_INVALID, "null argument");
-  return xv_copy_blob(m, m->params, host_blob, n, false);
-  X_CATCH
-}
-int32_t vitx_crossvit_get_grads(vitx_crossvit_handle m, float* host_blob, int64_t n) {
-  X_TRY
-  if (!m || !host_blob) return capi_fail(VITX_ERR_INVALID, "null argument");
-  return xv_copy_blob(m, m->grads, host_blob, n, false);
-  X_CATCH
-}
-int32_t vitx_crossvit_params_dev(vitx_crossvit_handle m, float** dev_ptr, int64_t* n_elems) {
-  if (!m || !dev_ptr) return capi_fail(VITX_ERR_INVALID, "null argument");
-  *dev_ptr = m->params;
-  if (n_elems) *n_elems = m->n_arena;
-  return VITX_OK;
-}
-int32_t vitx_crossvit_grads_dev(vitx_crossvit_handle m, float** dev_ptr, int64_t* n_elems) {
-  if (!m || !dev_ptr) return capi_fail(VITX_ERR_INVALID, "null argument");
-  *dev_ptr = m->grads;
-  if (n_elems) *n_elems = m->n_arena;
-  return VITX_OK;
-}
-int32_t vitx_crossvit_params_changed(vitx_crossvit_handle m) {
-  X_TRY
-  if (!m) return capi_fail(VITX_ERR_INVALID, "null handle");
-  std::string err;
-  int rc = push_params(m, err);
-  if (rc != VITX_OK) return capi_fail(rc, err);
-  return VITX_OK;
-  X_CATCH
-}
+COMPOSITE_ARENA_EXPORTS(vitx_crossvit, "blob size does not match the CrossViT parameter table")
 int32_t vitx_crossvit_forward_dev(vitx_crossvit_handle m, const float* img_dev, int32_t b, int32_t H, int32_t W, int32_t training, uint64_t seed,
                                   float* logits_dev_or_null) {
-  X_TRY
+  CAPI_TRY
   if (!m || !img_dev) return capi_fail(VITX_ERR_INVALID, "null argument");
   std::string err;
   int rc = crossvit_forward(m, img_dev, b, H, W, training, seed, err);
   if (rc != VITX_OK) return capi_fail(rc, err);
-  if (logits_dev_or_null) X_HIP(hipMemcpyAsync(logits_dev_or_null, m->logits, (size_t)b * m->nc * 4, hipMemcpyDeviceToDevice, m->stream));
+  if (logits_dev_or_null) CAPI_HIP(hipMemcpyAsync(logits_dev_or_null, m->logits, (size_t)b * m->nc * 4, hipMemcpyDeviceToDevice, m->stream));
   return VITX_OK;
-  X_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_crossvit_forward(vitx_crossvit_handle m, const float* img_host, int32_t b, int32_t H, int32_t W, int32_t training, uint64_t seed,
                               float* logits_host) {
-  X_TRY
+  CAPI_TRY
   if (!m || !img_host || !logits_host) return capi_fail(VITX_ERR_INVALID, "null argument");
   if (b <= 0 || b > m->cfg.max_batch) return capi_fail(VITX_ERR_INVALID, "batch must be in [1, max_batch]");
   if (H <= 0 || W <= 0 || H > m->cfg.image_size || W > m->cfg.image_size) return capi_fail(VITX_ERR_INVALID, "image larger than the configured image_size");
-  X_HIP(hipMemcpyAsync(m->img, img_host, (size_t)b * H * W * 3 * 4, hipMemcpyHostToDevice, m->stream));
+  CAPI_HIP(hipMemcpyAsync(m->img, img_host, (size_t)b * H * W * 3 * 4, hipMemcpyHostToDevice, m->stream));
   std::string err;
   int rc = crossvit_forward(m, m->img, b, H, W, training, seed, err);
   if (rc != VITX_OK) return capi_fail(rc, err);
-  X_HIP(hipMemcpyAsync(logits_host, m->logits, (size_t)b * m->nc * 4, hipMemcpyDeviceToHost, m->stream));
-  X_HIP(hipStreamSynchronize(m->stream));
+  CAPI_HIP(hipMemcpyAsync(logits_host, m->logits, (size_t)b * m->nc * 4, hipMemcpyDeviceToHost, m->stream));
+  CAPI_HIP(hipStreamSynchronize(m->stream));
   return VITX_OK;
-  X_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_crossvit_backward_dev(vitx_crossvit_handle m, const float* dlogits_dev, float* dimg_dev_or_null) {
-  X_TRY
+  CAPI_TRY
   if (!m || !dlogits_dev) return capi_fail(VITX_ERR_INVALID, "null argument");
   std::string err;
   int rc = crossvit_backward(m, dlogits_dev, dimg_dev_or_null, err);
   if (rc != VITX_OK) return capi_fail(rc, err);
   return VITX_OK;
-  X_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_crossvit_backward(vitx_crossvit_handle m, const float* dlogits_host, float* dimg_host_or_null) {
-  X_TRY
+  CAPI_TRY
   if (!m || !dlogits_host) return capi_fail(VITX_ERR_INVALID, "null argument");
   if (!m->have_fwd) return capi_fail(VITX_ERR_STATE, "backward requires a preceding forward");
-  X_HIP(hipMemcpyAsync(m->dlogits, dlogits_host, (size_t)m->b * m->nc * 4, hipMemcpyHostToDevice, m->stream));
+  CAPI_HIP(hipMemcpyAsync(m->dlogits, dlogits_host, (size_t)m->b * m->nc * 4, hipMemcpyHostToDevice, m->stream));
   std::string err;
   int rc = crossvit_backward(m, m->dlogits, dimg_host_or_null ? m->dimg : nullptr, err);
   if (rc != VITX_OK) return capi_fail(rc, err);
   if (dimg_host_or_null)
-    X_HIP(hipMemcpyAsync(dimg_host_or_null, m->dimg, (size_t)m->b * m->H * m->W * 3 * 4, hipMemcpyDeviceToHost, m->stream));
-  X_HIP(hipStreamSynchronize(m->stream));
+    CAPI_HIP(hipMemcpyAsync(dimg_host_or_null, m->dimg, (size_t)m->b * m->H * m->W * 3 * 4, hipMemcpyDeviceToHost, m->stream));
+  CAPI_HIP(hipStreamSynchronize(m->stream));
   return VITX_OK;
-  X_CATCH
+  CAPI_CATCH
 }
 // "sm_tokens" / "lg_tokens": the final tokens [b, n, dim] (after the last cross layer); "sm_logits" / "lg_logits": the two heads
 int32_t vitx_crossvit_read(vitx_crossvit_handle m, const char* which, float* out_host, int64_t cap, int64_t* n_elems) {
-  X_TRY
+  CAPI_TRY
   if (!m || !which || !out_host) return capi_fail(VITX_ERR_INVALID, "null argument");
   if (!m->have_fwd) return capi_fail(VITX_ERR_STATE, "read requires a preceding forward");
   const std::string w = which;
@@ -895,10 +756,10 @@ int32_t vitx_crossvit_read(vitx_crossvit_handle m, const char* which, float* out
   else return capi_fail(VITX_ERR_INVALID, "unknown tensor name");
   if (n_elems) *n_elems = n;
   if (n > cap) return capi_fail(VITX_ERR_INVALID, "output buffer too small");
-  X_HIP(hipMemcpyAsync(out_host, src, (size_t)n * 4, hipMemcpyDeviceToHost, m->stream));
-  X_HIP(hipStreamSynchronize(m->stream));
+  CAPI_HIP(hipMemcpyAsync(out_host, src, (size_t)n * 4, hipMemcpyDeviceToHost, m->stream));
+  CAPI_HIP(hipStreamSynchronize(m->stream));
   return VITX_OK;
-  X_CATCH
+  CAPI_CATCH
 }
 
 }  // extern "C"

@@ -6,18 +6,7 @@
 #include <algorithm>
 #include <cstring>
 
-#include "engine.h"
-
-int capi_fail(int code, const std::string& msg);   // capi.hip
-
-#define HIPCHK(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) {                                                                         \
-      err = std::string(#x) + ": " + hipGetErrorString(e_);                                         \
-      return VITX_ERR_HIP;                                                                          \
-    }                                                                                               \
-  } while (0)
+#include "composite.h"
 
 struct vitx_distill {
   vitx_distill_config cfg{};
@@ -27,7 +16,7 @@ struct vitx_distill {
   float *params = nullptr, *grads = nullptr;
   int64_t tok = -1, ln_g = -1, ln_b = -1, w = -1, bias = -1;
   int d = 0, nc = 0, B = 0;
-  std::vector<void*> allocs;
+  DevicePool pool;
   float *img = nullptr, *labels = nullptr, *teacher = nullptr, *slog = nullptr, *dtok = nullptr, *yh = nullptr, *dlog = nullptr, *mean = nullptr,
         *rstd = nullptr;
   float *u_student = nullptr, *u_distill = nullptr;   // gradients for a unit cotangent, scaled at backward time
@@ -130,34 +119,7 @@ __global__ void scale_rows_kernel(const float* __restrict__ unit, const float* _
   out[e] = unit[e] * coef[e / nc];
 }
 
-int64_t add_param(vitx_distill* m, const std::string& name, std::vector<int64_t> shape) {
-  ParamDesc p;
-  p.name = name; p.shape = shape; p.count = 1;
-  for (int64_t s : shape) p.count *= s;
-  p.offset = m->n_params; p.aoff = m->n_arena;
-  m->n_params += p.count;
-  m->n_arena += round_up(p.count, 4);
-  m->table.push_back(p);
-  return p.aoff;
-}
-
-int dist_alloc(vitx_distill* m, void** p, size_t bytes, std::string& err) {
-  bytes = (size_t)round_up((int64_t)std::max<size_t>(bytes, 16), 256);
-  HIPCHK(hipMalloc(p, bytes));
-  HIPCHK(hipMemsetAsync(*p, 0, bytes, m->stu->stream));
-  m->allocs.push_back(*p);
-  return VITX_OK;
-}
-#define DMALLOC(ptr, bytes)                                         \
-  do {                                                              \
-    int rc_ = dist_alloc(m, (void**)&(ptr), (size_t)(bytes), err);  \
-    if (rc_ != VITX_OK) return rc_;                                 \
-  } while (0)
-
-bool al16(std::initializer_list<const void*> ps) {
-  for (const void* p : ps) if (p && ((uintptr_t)p & 15)) return false;
-  return true;
-}
+#define DMALLOC(ptr, bytes) POOL_ALLOC(m->pool, ptr, bytes, m->stu->stream, rc_)
 
 int distill_create(vitx_engine* stu, const vitx_distill_config& cfg, vitx_distill** out, std::string& err) {
   if (stu->cfg.variant == VITX_VARIANT_CAIT || stu->cfg.variant == VITX_VARIANT_PATCH_MERGER) { err = "student must be a vision transformer"; return VITX_ERR_INVALID; }   // distill.py:91 (Distillable* classes)
@@ -166,11 +128,13 @@ int distill_create(vitx_engine* stu, const vitx_distill_config& cfg, vitx_distil
   m->cfg = cfg; m->stu = stu;
   m->d = stu->cfg.dim; m->nc = stu->cfg.num_classes; m->B = stu->cfg.max_batch;
   // attribute order of DistillWrapper.__init__ (distill.py:101-106)
-  m->tok = add_param(m, "distillation_token", {1, 1, m->d});
-  m->ln_g = add_param(m, "distill_mlp.norm.gamma", {m->d});
-  m->ln_b = add_param(m, "distill_mlp.norm.beta", {m->d});
-  m->w = add_param(m, "distill_mlp.kernel", {m->d, m->nc});
-  m->bias = add_param(m, "distill_mlp.bias", {m->nc});
+  TableBuilder tb{m->table};
+  m->tok = tb.add("distillation_token", {1, 1, m->d});
+  m->ln_g = tb.add("distill_mlp.norm.gamma", {m->d});
+  m->ln_b = tb.add("distill_mlp.norm.beta", {m->d});
+  m->w = tb.add("distill_mlp.kernel", {m->d, m->nc});
+  m->bias = tb.add("distill_mlp.bias", {m->nc});
+  m->n_params = tb.n; m->n_arena = tb.n_arena;
   const int64_t B = m->B, d = m->d, nc = m->nc;
   DMALLOC(m->params, (size_t)m->n_arena * 4);
   DMALLOC(m->grads, (size_t)m->n_arena * 4);
@@ -190,7 +154,7 @@ int distill_create(vitx_engine* stu, const vitx_distill_config& cfg, vitx_distil
 void distill_destroy(vitx_distill* m) {
   if (!m) return;
   (void)hipDeviceSynchronize();
-  for (void* p : m->allocs) (void)hipFree(p);
+  m->pool.free_all();
   delete m;
 }
 
@@ -207,14 +171,7 @@ int distill_forward(vitx_distill* m, const float* img_dev, const float* labels_d
   int rc;
   if ((rc = engine_forward(e, img_dev, b, H, W, training, seed, m->slog, err, P + m->tok, m->dtok)) != VITX_OK) return rc;   // distill.py:116
   launch_layernorm_fwd(m->dtok, d, P + m->ln_g, P + m->ln_b, m->yh, 0, d, m->mean, m->rstd, b, d, e->cfg.ln_eps, s);     // distill.py:104
-  {                                                                                                                   // distill.py:105
-    GenericGemmArgs g;
-    g.A = m->yh; g.B = P + m->w; g.M = b; g.N = nc; g.K = d; g.sam = d; g.sak = 1; g.sbk = nc; g.sbn = 1;
-    EpiParams ep;
-    ep.out = m->dlog; ep.ldo = nc; ep.M = b; ep.N = nc; ep.bias = P + m->bias;
-    ep.vec_ok = (nc % 4 == 0) && al16({m->dlog, ep.bias});
-    launch_gemm_generic(g, ep, EPI_STORE_F32, 0, 0, 0, s);
-  }
+  dense_fwd(m->yh, d, P + m->w, P + m->bias, m->dlog, b, nc, d, s);                                                     // distill.py:105
   hipLaunchKernelGGL(distill_loss_kernel, dim3((unsigned)b), dim3(64), 0, s, m->slog, labels_dev, m->dlog, teacher_dev, b, nc, m->T, m->cfg.hard,
                      m->cfg.literal_loss, m->ce, m->term, m->u_student, m->u_distill);
   hipLaunchKernelGGL(distill_combine_kernel, dim3(1), dim3(64), 0, s, m->ce, m->term, b, m->alpha, m->T, m->cfg.hard, m->loss);
@@ -245,16 +202,8 @@ int distill_backward(vitx_distill* m, const float* dloss_host, std::string& err,
   hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, m->u_distill, m->coef + b, (int64_t)b, nc, m->g_dlog);
   launch_fill_zero(G, m->n_arena * 4, s);
   {  // distill_mlp Dense: d yh = dL W^T, dW = yh^T dL, db = column sums
-    GenericGemmArgs g;
-    g.A = m->g_dlog; g.B = P + m->w; g.M = b; g.N = d; g.K = nc; g.sam = nc; g.sak = 1; g.sbk = 1; g.sbn = nc;
-    EpiParams ep;
-    ep.out = m->g_yh; ep.ldo = d; ep.M = b; ep.N = d; ep.vec_ok = (d % 4 == 0) && al16({m->g_yh});
-    launch_gemm_generic(g, ep, EPI_STORE_F32, 0, 0, 0, s);
-    GenericGemmArgs w;
-    w.A = m->yh; w.B = m->g_dlog; w.M = d; w.N = nc; w.K = b; w.sam = 1; w.sak = d; w.sbk = nc; w.sbn = 1;
-    EpiParams ew;
-    ew.out = G + m->w; ew.ldo = nc; ew.M = d; ew.N = nc; ew.vec_ok = (nc % 4 == 0) && al16({ew.out});
-    launch_gemm_generic(w, ew, EPI_STORE_F32, 0, 0, 0, s);
+    dense_dx(m->g_dlog, P + m->w, m->g_yh, b, nc, d, s);
+    dense_dw(m->yh, d, m->g_dlog, G + m->w, b, nc, d, s);
     launch_colsum(m->g_dlog, 0, nc, b, nc, m->ws, G + m->bias, s);
   }
   launch_layernorm_bwd(m->g_yh, 0, d, m->dtok, d, m->mean, m->rstd, P + m->ln_g, nullptr, 0, m->g_dtok, d, nullptr, 0, m->ws, G + m->ln_g, G + m->ln_b,
@@ -263,17 +212,6 @@ int distill_backward(vitx_distill* m, const float* dloss_host, std::string& err,
 }
 
 }  // namespace
-
-#define D_TRY try {
-#define D_CATCH                                                                       \
-  }                                                                                   \
-  catch (const std::exception& ex) { return capi_fail(VITX_ERR_INVALID, ex.what()); } \
-  catch (...) { return capi_fail(VITX_ERR_INVALID, "unknown C++ exception"); }
-#define D_HIP(x)                                                                                           \
-  do {                                                                                                     \
-    hipError_t e_ = (x);                                                                                   \
-    if (e_ != hipSuccess) return capi_fail(VITX_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_));  \
-  } while (0)
 
 static float* distill_scratch(vitx_engine* h) {
   if (!h->distill_ws) {
@@ -290,7 +228,7 @@ extern "C" {
 // ---- DistillableViT.call(img, distill_token) (distill.py:16-44) and its VJP on host buffers
 int32_t vitx_forward_distill(vitx_handle h, const float* img_host, int32_t b, int32_t H, int32_t W, int32_t training, uint64_t seed,
                              const float* distill_token_host, float* logits_host, float* distill_tokens_host) {
-  D_TRY
+  CAPI_TRY
   const int np_in = h ? h->next_patch_np : 0;   // > 0: img_host holds patch rows [b, np, patch_dim] (vitx_set_patch_input, one shot: consumed
   if (h) h->next_patch_np = 0;                  //   before any validation can fail, so that a rejected call does not leave the handle armed)
   if (!h || !img_host || !distill_token_host || !logits_host || !distill_tokens_host) return capi_fail(VITX_ERR_INVALID, "null argument");
@@ -301,47 +239,47 @@ int32_t vitx_forward_distill(vitx_handle h, const float* img_host, int32_t b, in
   float* tok = distill_scratch(h);   // row 0 = the token, rows 1.. = the returned per-image tokens
   if (!tok) return capi_fail(VITX_ERR_HIP, "hipMalloc failed");
   const size_t in_elems = np_in ? (size_t)b * np_in * h->pd : (size_t)b * H * W * h->cfg.channels;
-  D_HIP(hipMemcpyAsync(h->img_dev, img_host, in_elems * 4, hipMemcpyHostToDevice, s));
-  D_HIP(hipMemcpyAsync(tok, distill_token_host, (size_t)d * 4, hipMemcpyHostToDevice, s));
+  CAPI_HIP(hipMemcpyAsync(h->img_dev, img_host, in_elems * 4, hipMemcpyHostToDevice, s));
+  CAPI_HIP(hipMemcpyAsync(tok, distill_token_host, (size_t)d * 4, hipMemcpyHostToDevice, s));
   std::string err;
   if (np_in) { h->fwd_patches = h->img_dev; h->fwd_np = np_in; }   // set right before the call that consumes it: no error exit in between
   int rc = engine_forward(h, h->img_dev, b, H, W, training, seed, nullptr, err, tok, tok + d);
   h->fwd_patches = nullptr;
   if (rc != VITX_OK) return capi_fail(rc, err);
-  D_HIP(hipMemcpy2DAsync(logits_host, (size_t)nc * 4, h->logits, (size_t)h->nc_k * 4, (size_t)nc * 4, (size_t)b, hipMemcpyDeviceToHost, s));
-  D_HIP(hipMemcpyAsync(distill_tokens_host, tok + d, (size_t)b * d * 4, hipMemcpyDeviceToHost, s));
-  D_HIP(hipStreamSynchronize(s));
+  CAPI_HIP(hipMemcpy2DAsync(logits_host, (size_t)nc * 4, h->logits, (size_t)h->nc_k * 4, (size_t)nc * 4, (size_t)b, hipMemcpyDeviceToHost, s));
+  CAPI_HIP(hipMemcpyAsync(distill_tokens_host, tok + d, (size_t)b * d * 4, hipMemcpyDeviceToHost, s));
+  CAPI_HIP(hipStreamSynchronize(s));
   return VITX_OK;
-  D_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_backward_distill(vitx_handle h, const float* dlogits_host, const float* d_distill_tokens_host, float* d_distill_token_host,
                               float* dimg_host_or_null) {
-  D_TRY
+  CAPI_TRY
   if (!h || !dlogits_host) return capi_fail(VITX_ERR_INVALID, "null argument");
   if (!h->have_fwd || !h->last_extra) return capi_fail(VITX_ERR_STATE, "backward_distill requires a preceding forward_distill");
   const int b = h->last_b, nc = h->cfg.num_classes, d = h->cfg.dim;
   hipStream_t s = h->stream;
   float* tok = distill_scratch(h);
   if (!tok) return capi_fail(VITX_ERR_HIP, "hipMalloc failed");
-  D_HIP(hipMemcpy2DAsync(h->dlogits, (size_t)h->nc_k * 4, dlogits_host, (size_t)nc * 4, (size_t)nc * 4, (size_t)b, hipMemcpyHostToDevice, s));
-  if (d_distill_tokens_host) D_HIP(hipMemcpyAsync(tok + d, d_distill_tokens_host, (size_t)b * d * 4, hipMemcpyHostToDevice, s));
+  CAPI_HIP(hipMemcpy2DAsync(h->dlogits, (size_t)h->nc_k * 4, dlogits_host, (size_t)nc * 4, (size_t)nc * 4, (size_t)b, hipMemcpyHostToDevice, s));
+  if (d_distill_tokens_host) CAPI_HIP(hipMemcpyAsync(tok + d, d_distill_tokens_host, (size_t)b * d * 4, hipMemcpyHostToDevice, s));
   float* dimg_dev = dimg_host_or_null ? h->img_dev : nullptr;
   std::string err;
   float* dd = d_distill_tokens_host ? tok + d : nullptr;
   float* dt = tok;
   int rc = engine_backward(h, nullptr, dimg_dev, err, dd, dt);
   if (rc != VITX_OK) return capi_fail(rc, err);
-  if (d_distill_token_host) D_HIP(hipMemcpyAsync(d_distill_token_host, dt, (size_t)d * 4, hipMemcpyDeviceToHost, s));
+  if (d_distill_token_host) CAPI_HIP(hipMemcpyAsync(d_distill_token_host, dt, (size_t)d * 4, hipMemcpyDeviceToHost, s));
   if (dimg_host_or_null)
-    D_HIP(hipMemcpyAsync(dimg_host_or_null, dimg_dev, (size_t)b * h->last_H * h->last_W * h->cfg.channels * 4, hipMemcpyDeviceToHost, s));
-  D_HIP(hipStreamSynchronize(s));
+    CAPI_HIP(hipMemcpyAsync(dimg_host_or_null, dimg_dev, (size_t)b * h->last_H * h->last_W * h->cfg.channels * 4, hipMemcpyDeviceToHost, s));
+  CAPI_HIP(hipStreamSynchronize(s));
   return VITX_OK;
-  D_CATCH
+  CAPI_CATCH
 }
 
 // ---- DistillWrapper (distill.py:87-134)
 int32_t vitx_distill_create(vitx_handle student, const vitx_distill_config* cfg, vitx_distill_handle* out) {
-  D_TRY
+  CAPI_TRY
   if (!student || !cfg || !out) return capi_fail(VITX_ERR_INVALID, "null argument");
   if (student->cfg.small_dataset) return capi_fail(VITX_ERR_UNSUPPORTED, "distill_create: small_dataset students are not supported");
   std::string err;
@@ -350,13 +288,13 @@ int32_t vitx_distill_create(vitx_handle student, const vitx_distill_config* cfg,
   if (rc != VITX_OK) return capi_fail(rc, err);
   *out = m;
   return VITX_OK;
-  D_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_distill_destroy(vitx_distill_handle m) {
-  D_TRY
+  CAPI_TRY
   distill_destroy(m);
   return VITX_OK;
-  D_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_distill_param_table_size(vitx_distill_handle m, int64_t* n_tensors, int64_t* n_elems) {
   if (!m) return capi_fail(VITX_ERR_INVALID, "null handle");
@@ -367,46 +305,33 @@ int32_t vitx_distill_param_table_size(vitx_distill_handle m, int64_t* n_tensors,
 int32_t vitx_distill_param_table_entry(vitx_distill_handle m, int64_t index, char* name, int32_t name_cap, int64_t shape[4], int32_t* rank,
                                        int64_t* offset_elems) {
   if (!m) return capi_fail(VITX_ERR_INVALID, "null handle");
-  if (index < 0 || index >= (int64_t)m->table.size()) return capi_fail(VITX_ERR_INVALID, "parameter index out of range");
-  const ParamDesc& p = m->table[(size_t)index];
-  if (name && name_cap > 0) { std::strncpy(name, p.name.c_str(), (size_t)name_cap - 1); name[name_cap - 1] = 0; }
-  if (shape) for (int i = 0; i < 4; ++i) shape[i] = i < (int)p.shape.size() ? p.shape[(size_t)i] : 1;
-  if (rank) *rank = (int32_t)p.shape.size();
-  if (offset_elems) *offset_elems = p.offset;
-  return VITX_OK;
+  return write_table_entry(m->table, index, name, name_cap, shape, rank, offset_elems);
 }
 static int dist_copy_blob(vitx_distill* m, float* arena, float* host, int64_t n, bool to_device) {
-  if (n != m->n_params) return capi_fail(VITX_ERR_INVALID, "blob size does not match the wrapper's parameter table");
-  hipStream_t s = m->stu->stream;
-  for (auto& p : m->table) {
-    if (to_device) D_HIP(hipMemcpyAsync(arena + p.aoff, host + p.offset, (size_t)p.count * 4, hipMemcpyHostToDevice, s));
-    else D_HIP(hipMemcpyAsync(host + p.offset, arena + p.aoff, (size_t)p.count * 4, hipMemcpyDeviceToHost, s));
-  }
-  D_HIP(hipStreamSynchronize(s));
-  return VITX_OK;
+  return copy_param_blob(m->table, m->n_params, arena, host, n, to_device, m->stu->stream, "blob size does not match the wrapper's parameter table");
 }
 int32_t vitx_distill_set_params(vitx_distill_handle m, const float* host_blob, int64_t n) {
-  D_TRY
+  CAPI_TRY
   if (!m || !host_blob) return capi_fail(VITX_ERR_INVALID, "null argument");
   return dist_copy_blob(m, m->params, const_cast<float*>(host_blob), n, true);
-  D_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_distill_get_params(vitx_distill_handle m, float* host_blob, int64_t n) {
-  D_TRY
+  CAPI_TRY
   if (!m || !host_blob) return capi_fail(VITX_ERR_INVALID, "null argument");
   return dist_copy_blob(m, m->params, host_blob, n, false);
-  D_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_distill_get_grads(vitx_distill_handle m, float* host_blob, int64_t n) {
-  D_TRY
+  CAPI_TRY
   if (!m || !host_blob) return capi_fail(VITX_ERR_INVALID, "null argument");
   return dist_copy_blob(m, m->grads, host_blob, n, false);
-  D_CATCH
+  CAPI_CATCH
 }
 
 int32_t vitx_distill_forward(vitx_distill_handle m, const float* img_host, const float* labels_host, const float* teacher_logits_host, int32_t b,
                              int32_t H, int32_t W, int32_t training, uint64_t seed, float temperature, float alpha, float* loss_host) {
-  D_TRY
+  CAPI_TRY
   const int np_in = (m && m->stu) ? m->stu->next_patch_np : 0;   // > 0: img_host holds patch rows [b, np, patch_dim] (vitx_set_patch_input on the
   if (m && m->stu) m->stu->next_patch_np = 0;                    //   student, one shot: consumed before any validation can fail)
   if (!m || !img_host || !labels_host || !teacher_logits_host) return capi_fail(VITX_ERR_INVALID, "null argument");
@@ -415,55 +340,55 @@ int32_t vitx_distill_forward(vitx_distill_handle m, const float* img_host, const
   if (!np_in && (H <= 0 || W <= 0 || H > c.image_h || W > c.image_w)) return capi_fail(VITX_ERR_INVALID, "image larger than the configured image_size");
   hipStream_t s = m->stu->stream;
   const size_t in_elems = np_in ? (size_t)b * np_in * m->stu->pd : (size_t)b * H * W * c.channels;
-  D_HIP(hipMemcpyAsync(m->img, img_host, in_elems * 4, hipMemcpyHostToDevice, s));
-  D_HIP(hipMemcpyAsync(m->labels, labels_host, (size_t)b * m->nc * 4, hipMemcpyHostToDevice, s));
-  D_HIP(hipMemcpyAsync(m->teacher, teacher_logits_host, (size_t)b * m->nc * 4, hipMemcpyHostToDevice, s));
+  CAPI_HIP(hipMemcpyAsync(m->img, img_host, in_elems * 4, hipMemcpyHostToDevice, s));
+  CAPI_HIP(hipMemcpyAsync(m->labels, labels_host, (size_t)b * m->nc * 4, hipMemcpyHostToDevice, s));
+  CAPI_HIP(hipMemcpyAsync(m->teacher, teacher_logits_host, (size_t)b * m->nc * 4, hipMemcpyHostToDevice, s));
   std::string err;
   if (np_in) { m->stu->fwd_patches = m->img; m->stu->fwd_np = np_in; }   // set right before the call that consumes it
   int rc = distill_forward(m, m->img, m->labels, m->teacher, b, H, W, training, seed, temperature, alpha, err);
   m->stu->fwd_patches = nullptr;                                          // (also when distill_forward failed before reaching the engine)
   if (rc != VITX_OK) return capi_fail(rc, err);
-  if (loss_host) D_HIP(hipMemcpyAsync(loss_host, m->loss, (size_t)b * 4, hipMemcpyDeviceToHost, s));
-  D_HIP(hipStreamSynchronize(s));
+  if (loss_host) CAPI_HIP(hipMemcpyAsync(loss_host, m->loss, (size_t)b * 4, hipMemcpyDeviceToHost, s));
+  CAPI_HIP(hipStreamSynchronize(s));
   return VITX_OK;
-  D_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_distill_forward_dev(vitx_distill_handle m, const float* img_dev, const float* labels_dev, const float* teacher_logits_dev, int32_t b,
                                  int32_t H, int32_t W, int32_t training, uint64_t seed, float temperature, float alpha, float* loss_dev_or_null) {
-  D_TRY
+  CAPI_TRY
   if (!m || !img_dev || !labels_dev || !teacher_logits_dev) return capi_fail(VITX_ERR_INVALID, "null argument");
   std::string err;
   int rc = distill_forward(m, img_dev, labels_dev, teacher_logits_dev, b, H, W, training, seed, temperature, alpha, err);
   if (rc != VITX_OK) return capi_fail(rc, err);
-  if (loss_dev_or_null) D_HIP(hipMemcpyAsync(loss_dev_or_null, m->loss, (size_t)b * 4, hipMemcpyDeviceToDevice, m->stu->stream));
+  if (loss_dev_or_null) CAPI_HIP(hipMemcpyAsync(loss_dev_or_null, m->loss, (size_t)b * 4, hipMemcpyDeviceToDevice, m->stu->stream));
   return VITX_OK;
-  D_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_distill_backward(vitx_distill_handle m, const float* dloss_host_or_null) {
-  D_TRY
+  CAPI_TRY
   if (!m) return capi_fail(VITX_ERR_INVALID, "null handle");
   std::string err;
   int rc = distill_backward(m, dloss_host_or_null, err);
   if (rc != VITX_OK) return capi_fail(rc, err);
   return VITX_OK;
-  D_CATCH
+  CAPI_CATCH
 }
 // the same, also returning d(loss)/d(input) of the student's forward: d(img) [b, H, W, C], or d(patches) [b, np, patch_dim] when that
 // forward took patch rows (a T2T-ViT student: the tokenizer in front of the handle needs it to continue the chain)
 int32_t vitx_distill_backward_input(vitx_distill_handle m, const float* dloss_host_or_null, float* dinput_host) {
-  D_TRY
+  CAPI_TRY
   if (!m || !dinput_host) return capi_fail(VITX_ERR_INVALID, "null argument");
   std::string err;
   int rc = distill_backward(m, dloss_host_or_null, err, m->img);
   if (rc != VITX_OK) return capi_fail(rc, err);
   vitx_engine* e = m->stu;
-  D_HIP(hipMemcpyAsync(dinput_host, m->img, (size_t)e->last_b * e->last_H * e->last_W * e->cfg.channels * 4, hipMemcpyDeviceToHost, e->stream));
-  D_HIP(hipStreamSynchronize(e->stream));
+  CAPI_HIP(hipMemcpyAsync(dinput_host, m->img, (size_t)e->last_b * e->last_H * e->last_W * e->cfg.channels * 4, hipMemcpyDeviceToHost, e->stream));
+  CAPI_HIP(hipStreamSynchronize(e->stream));
   return VITX_OK;
-  D_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_distill_read(vitx_distill_handle m, const char* which, float* out_host, int64_t cap, int64_t* n_elems) {
-  D_TRY
+  CAPI_TRY
   if (!m || !which || !out_host) return capi_fail(VITX_ERR_INVALID, "null argument");
   if (!m->have_fwd) return capi_fail(VITX_ERR_STATE, "read requires a preceding forward");
   const std::string w = which;
@@ -475,10 +400,10 @@ int32_t vitx_distill_read(vitx_distill_handle m, const char* which, float* out_h
   else return capi_fail(VITX_ERR_INVALID, "unknown tensor name");
   if (n_elems) *n_elems = n;
   if (n > cap) return capi_fail(VITX_ERR_INVALID, "output buffer too small");
-  D_HIP(hipMemcpyAsync(out_host, src, (size_t)n * 4, hipMemcpyDeviceToHost, m->stu->stream));
-  D_HIP(hipStreamSynchronize(m->stu->stream));
+  CAPI_HIP(hipMemcpyAsync(out_host, src, (size_t)n * 4, hipMemcpyDeviceToHost, m->stu->stream));
+  CAPI_HIP(hipStreamSynchronize(m->stu->stream));
   return VITX_OK;
-  D_CATCH
+  CAPI_CATCH
 }
 
 }  // extern "C"

@@ -8,18 +8,7 @@
 #include <cstring>
 #include <algorithm>
 
-#include "engine.h"
-
-int capi_fail(int code, const std::string& msg);   // capi.hip (thread-local last-error text)
-
-#define HIPCHK(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) {                                                                         \
-      err = std::string(#x) + ": " + hipGetErrorString(e_);                                         \
-      return VITX_ERR_HIP;                                                                          \
-    }                                                                                               \
-  } while (0)
+#include "composite.h"
 
 struct vitx_mim {
   vitx_mim_config cfg{};
@@ -35,7 +24,7 @@ struct vitx_mim {
   int po = 0;                         // output width of the wrapper's last Dense: patch_dim (to_pixels) or 2^(bits * channels) (to_bits)
   float *tok1 = nullptr, *enc1 = nullptr;   // MPP: [B, np + 1, d] embedded tokens / transformer output (cls row included)
   int32_t* labels = nullptr;          // MPP, literal_loss = 0: class of each masked patch
-  std::vector<void*> allocs;
+  DevicePool pool;
   float *img = nullptr, *patches = nullptr, *tok = nullptr, *sel = nullptr, *enc_out = nullptr, *proj = nullptr, *dec_in = nullptr,
         *dec_out = nullptr, *rows_m = nullptr, *pred = nullptr, *target = nullptr, *dpred = nullptr;
   float *g_rows_m = nullptr, *g_a = nullptr, *g_b = nullptr, *g_c = nullptr;   // backward scratch ([B*np, max(d,dd)] each)
@@ -59,86 +48,42 @@ int mim_num_masked(const vitx_mim* m, int np) {
   return (int)(m->cfg.masking_ratio * (double)np);
 }
 
-int64_t add_param(vitx_mim* m, const std::string& name, std::vector<int64_t> shape) {
-  ParamDesc p;
-  p.name = name; p.shape = shape; p.count = 1;
-  for (int64_t s : shape) p.count *= s;
-  p.offset = m->n_params; p.aoff = m->n_arena;
-  m->n_params += p.count;
-  m->n_arena += round_up(p.count, 4);
-  m->table.push_back(p);
-  return p.aoff;
-}
-
 // ONE ordering rule for every parameter list of this library: a model's OWN variables first, then its sub-layers in
 // the attribute order of the reference constructor, kernel before bias -- what Keras 2's Layer.trainable_weights does (`self._trainable_weights +
 // children's`), as far as it can be stated without TensorFlow here (oracle/gen_ref_fixtures.py --real-tf prints the comparison where it exists).
 // Shapes are the reference variables' own: MPP's mask token is [1, 1, c p^2] (mpp.py:159), MAE's / SimMIM's are vectors (mae.py:42, simmim.py:83).
 void build_mim_table(vitx_mim* m) {
-  m->table.clear(); m->n_params = m->n_arena = 0;
+  m->table.clear();
+  TableBuilder tb{m->table};
   if (m->mpp) {   // mpp.py:159 (variable), mpp.py:149 (to_bits)
-    m->mask_tok = add_param(m, "mask_token", {1, 1, m->pd});
-    m->w_px = add_param(m, "to_bits.kernel", {m->d, m->po});
-    m->b_px = add_param(m, "to_bits.bias", {m->po});
+    m->mask_tok = tb.add("mask_token", {1, 1, m->pd});
+    m->w_px = tb.add("to_bits.kernel", {m->d, m->po});
+    m->b_px = tb.add("to_bits.bias", {m->po});
   } else if (m->mae) {   // mae.py:42 (variable), then mae.py:41,44,45
-    m->mask_tok = add_param(m, "mask_token", {m->dd});
-    if (m->project) { m->w_ed = add_param(m, "enc_to_dec.kernel", {m->d, m->dd}); m->b_ed = add_param(m, "enc_to_dec.bias", {m->dd}); }
+    m->mask_tok = tb.add("mask_token", {m->dd});
+    if (m->project) { m->w_ed = tb.add("enc_to_dec.kernel", {m->d, m->dd}); m->b_ed = tb.add("enc_to_dec.bias", {m->dd}); }
     // num_patches is read off pos_embedding.shape[-2] (mae.py:37), i.e. it counts the cls row: the table has np + 1 rows
-    m->dpos = add_param(m, "decoder_pos_emb.embeddings", {m->np_max + 1, m->dd});
-    m->w_px = add_param(m, "to_pixels.kernel", {m->dd, m->pd});
-    m->b_px = add_param(m, "to_pixels.bias", {m->pd});
+    m->dpos = tb.add("decoder_pos_emb.embeddings", {m->np_max + 1, m->dd});
+    m->w_px = tb.add("to_pixels.kernel", {m->dd, m->pd});
+    m->b_px = tb.add("to_pixels.bias", {m->pd});
   } else {
-    m->mask_tok = add_param(m, "mask_token", {m->d});
-    m->w_px = add_param(m, "to_pixels.kernel", {m->d, m->pd});
-    m->b_px = add_param(m, "to_pixels.bias", {m->pd});
+    m->mask_tok = tb.add("mask_token", {m->d});
+    m->w_px = tb.add("to_pixels.kernel", {m->d, m->pd});
+    m->b_px = tb.add("to_pixels.bias", {m->pd});
   }
+  m->n_params = tb.n; m->n_arena = tb.n_arena;
 }
 
-int mim_alloc(vitx_mim* m, void** p, size_t bytes, std::string& err) {
-  bytes = (size_t)round_up((int64_t)std::max<size_t>(bytes, 16), 256);
-  HIPCHK(hipMalloc(p, bytes));
-  HIPCHK(hipMemsetAsync(*p, 0, bytes, m->enc->stream));
-  m->allocs.push_back(*p);
-  return VITX_OK;
-}
-#define MALLOC(ptr, bytes)                                         \
-  do {                                                             \
-    int rc_ = mim_alloc(m, (void**)&(ptr), (size_t)(bytes), err);  \
-    if (rc_ != VITX_OK) return rc_;                                \
-  } while (0)
-
-bool aligned16(std::initializer_list<const void*> ps) {
-  for (const void* p : ps) if (p && ((uintptr_t)p & 15)) return false;
-  return true;
-}
+#define MALLOC(ptr, bytes) POOL_ALLOC(m->pool, ptr, bytes, m->enc->stream, rc_)
 
 // Keras Dense on fp32 rows: y = x @ W[in,out] + bias (mae.py:41,45,70,86; simmim.py:84,122), exact fp32 FMA chain
 void lin_fwd(const float* x, int rows, int in, const float* W, const float* bias, int out, float* y, hipStream_t s) {
-  GenericGemmArgs g;
-  g.A = x; g.B = W; g.M = rows; g.N = out; g.K = in; g.sam = in; g.sak = 1; g.sbk = out; g.sbn = 1;
-  EpiParams ep;
-  ep.out = y; ep.ldo = out; ep.M = rows; ep.N = out; ep.bias = bias;
-  ep.vec_ok = (out % 4 == 0) && aligned16({y, bias});
-  launch_gemm_generic(g, ep, EPI_STORE_F32, 0, 0, 0, s);
+  dense_fwd(x, in, W, bias, y, rows, out, in, s);
 }
 // VJP: dx = dy @ W^T (optional), dW = x^T @ dy, db = column sums of dy (optional)
 void lin_bwd(const float* x, const float* W, const float* dy, int rows, int in, int out, float* dx, float* dW, float* db, float* ws, hipStream_t s) {
-  if (dx) {
-    GenericGemmArgs g;
-    g.A = dy; g.B = W; g.M = rows; g.N = in; g.K = out; g.sam = out; g.sak = 1; g.sbk = 1; g.sbn = out;
-    EpiParams ep;
-    ep.out = dx; ep.ldo = in; ep.M = rows; ep.N = in;
-    ep.vec_ok = (in % 4 == 0) && aligned16({dx});
-    launch_gemm_generic(g, ep, EPI_STORE_F32, 0, 0, 0, s);
-  }
-  {
-    GenericGemmArgs g;
-    g.A = x; g.B = dy; g.M = in; g.N = out; g.K = rows; g.sam = 1; g.sak = in; g.sbk = out; g.sbn = 1;
-    EpiParams ep;
-    ep.out = dW; ep.ldo = out; ep.M = in; ep.N = out;
-    ep.vec_ok = (out % 4 == 0) && aligned16({dW});
-    launch_gemm_generic(g, ep, EPI_STORE_F32, 0, 0, 0, s);
-  }
+  if (dx) dense_dx(dy, W, dx, rows, out, in, s);
+  dense_dw(x, in, dy, dW, rows, out, in, s);
   if (db) launch_colsum(dy, 0, out, rows, out, ws, db, s);
 }
 
@@ -273,7 +218,7 @@ int mim_create(vitx_engine* enc, const vitx_mim_config& cfg, vitx_mim** out, std
 void mim_destroy(vitx_mim* m) {
   if (!m) return;
   (void)hipDeviceSynchronize();
-  for (void* p : m->allocs) (void)hipFree(p);
+  m->pool.free_all();
   if (m->dec) engine_destroy(m->dec);
   delete m;
 }
@@ -428,21 +373,10 @@ int check_indices(const vitx_mim* m, const int32_t* idx, int b, int np, int nm, 
 
 }  // namespace
 
-#define MIM_TRY try {
-#define MIM_CATCH                                                                    \
-  }                                                                                  \
-  catch (const std::exception& ex) { return capi_fail(VITX_ERR_INVALID, ex.what()); } \
-  catch (...) { return capi_fail(VITX_ERR_INVALID, "unknown C++ exception"); }
-#define MIM_HIP(x)                                                                                         \
-  do {                                                                                                     \
-    hipError_t e_ = (x);                                                                                   \
-    if (e_ != hipSuccess) return capi_fail(VITX_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_));  \
-  } while (0)
-
 extern "C" {
 
 int32_t vitx_mim_create(vitx_handle encoder, const vitx_mim_config* cfg, vitx_mim_handle* out) {
-  MIM_TRY
+  CAPI_TRY
   if (!encoder || !cfg || !out) return capi_fail(VITX_ERR_INVALID, "null argument");
   if (encoder->cfg.small_dataset) return capi_fail(VITX_ERR_UNSUPPORTED, "mim_create: small_dataset encoders are not supported");
   std::string err;
@@ -451,13 +385,13 @@ int32_t vitx_mim_create(vitx_handle encoder, const vitx_mim_config* cfg, vitx_mi
   if (rc != VITX_OK) return capi_fail(rc, err);
   *out = m;
   return VITX_OK;
-  MIM_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_mim_destroy(vitx_mim_handle m) {
-  MIM_TRY
+  CAPI_TRY
   mim_destroy(m);
   return VITX_OK;
-  MIM_CATCH
+  CAPI_CATCH
 }
 vitx_handle vitx_mim_decoder(vitx_mim_handle m) { return m ? m->dec : nullptr; }
 
@@ -470,43 +404,30 @@ int32_t vitx_mim_param_table_size(vitx_mim_handle m, int64_t* n_tensors, int64_t
 int32_t vitx_mim_param_table_entry(vitx_mim_handle m, int64_t index, char* name, int32_t name_cap, int64_t shape[4], int32_t* rank,
                                    int64_t* offset_elems) {
   if (!m) return capi_fail(VITX_ERR_INVALID, "null handle");
-  if (index < 0 || index >= (int64_t)m->table.size()) return capi_fail(VITX_ERR_INVALID, "parameter index out of range");
-  const ParamDesc& p = m->table[(size_t)index];
-  if (name && name_cap > 0) { std::strncpy(name, p.name.c_str(), (size_t)name_cap - 1); name[name_cap - 1] = 0; }
-  if (shape) for (int i = 0; i < 4; ++i) shape[i] = i < (int)p.shape.size() ? p.shape[(size_t)i] : 1;
-  if (rank) *rank = (int32_t)p.shape.size();
-  if (offset_elems) *offset_elems = p.offset;
-  return VITX_OK;
+  return write_table_entry(m->table, index, name, name_cap, shape, rank, offset_elems);
 }
 
 static int mim_copy_blob(vitx_mim* m, float* arena, float* host, int64_t n, bool to_device) {
-  if (n != m->n_params) return capi_fail(VITX_ERR_INVALID, "blob size does not match the wrapper's parameter table");
-  hipStream_t s = m->enc->stream;
-  for (auto& p : m->table) {
-    if (to_device) MIM_HIP(hipMemcpyAsync(arena + p.aoff, host + p.offset, (size_t)p.count * 4, hipMemcpyHostToDevice, s));
-    else MIM_HIP(hipMemcpyAsync(host + p.offset, arena + p.aoff, (size_t)p.count * 4, hipMemcpyDeviceToHost, s));
-  }
-  MIM_HIP(hipStreamSynchronize(s));
-  return VITX_OK;
+  return copy_param_blob(m->table, m->n_params, arena, host, n, to_device, m->enc->stream, "blob size does not match the wrapper's parameter table");
 }
 int32_t vitx_mim_set_params(vitx_mim_handle m, const float* host_blob, int64_t n) {
-  MIM_TRY
+  CAPI_TRY
   if (!m || !host_blob) return capi_fail(VITX_ERR_INVALID, "null argument");
   m->w_dirty = true;
   return mim_copy_blob(m, m->params, const_cast<float*>(host_blob), n, true);
-  MIM_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_mim_get_params(vitx_mim_handle m, float* host_blob, int64_t n) {
-  MIM_TRY
+  CAPI_TRY
   if (!m || !host_blob) return capi_fail(VITX_ERR_INVALID, "null argument");
   return mim_copy_blob(m, m->params, host_blob, n, false);
-  MIM_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_mim_get_grads(vitx_mim_handle m, float* host_blob, int64_t n) {
-  MIM_TRY
+  CAPI_TRY
   if (!m || !host_blob) return capi_fail(VITX_ERR_INVALID, "null argument");
   return mim_copy_blob(m, m->grads, host_blob, n, false);
-  MIM_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_mim_params_dev(vitx_mim_handle m, float** params_dev, float** grads_dev, int64_t* n_elems) {
   if (!m) return capi_fail(VITX_ERR_INVALID, "null handle");
@@ -533,17 +454,17 @@ int32_t vitx_mim_num_masked(vitx_mim_handle m, int32_t H, int32_t W, int32_t* nu
 }
 
 int32_t vitx_mim_forward_dev(vitx_mim_handle m, const float* img_dev, int32_t b, int32_t H, int32_t W, const int32_t* idx_dev, int32_t training, uint64_t seed, float* loss_dev) {
-  MIM_TRY
+  CAPI_TRY
   if (!m || !img_dev || !idx_dev) return capi_fail(VITX_ERR_INVALID, "null argument");
   std::string err;
   int rc = mim_forward(m, img_dev, b, H, W, idx_dev, training, seed, err);
   if (rc != VITX_OK) return capi_fail(rc, err);
-  if (loss_dev) MIM_HIP(hipMemcpyAsync(loss_dev, m->loss, 4, hipMemcpyDeviceToDevice, m->enc->stream));
+  if (loss_dev) CAPI_HIP(hipMemcpyAsync(loss_dev, m->loss, 4, hipMemcpyDeviceToDevice, m->enc->stream));
   return VITX_OK;
-  MIM_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_mim_forward(vitx_mim_handle m, const float* img_host, int32_t b, int32_t H, int32_t W, const int32_t* idx_host, int32_t training, uint64_t seed, float* loss_host) {
-  MIM_TRY
+  CAPI_TRY
   if (!m || !img_host || !idx_host) return capi_fail(VITX_ERR_INVALID, "null argument");
   const vitx_config& c = m->enc->cfg;
   if (b <= 0 || b > c.max_batch) return capi_fail(VITX_ERR_INVALID, "batch must be in [1, max_batch]");
@@ -554,27 +475,27 @@ int32_t vitx_mim_forward(vitx_mim_handle m, const float* img_host, int32_t b, in
   int rc = check_indices(m, idx_host, b, np, nm, err);
   if (rc != VITX_OK) return capi_fail(rc, err);
   hipStream_t s = m->enc->stream;
-  MIM_HIP(hipMemcpyAsync(m->img, img_host, (size_t)b * H * W * c.channels * 4, hipMemcpyHostToDevice, s));
-  MIM_HIP(hipMemcpyAsync(m->idx, idx_host, (size_t)b * (m->mae ? np : nm) * 4, hipMemcpyHostToDevice, s));
+  CAPI_HIP(hipMemcpyAsync(m->img, img_host, (size_t)b * H * W * c.channels * 4, hipMemcpyHostToDevice, s));
+  CAPI_HIP(hipMemcpyAsync(m->idx, idx_host, (size_t)b * (m->mae ? np : nm) * 4, hipMemcpyHostToDevice, s));
   rc = mim_forward(m, m->img, b, H, W, m->idx, training, seed, err);
   if (rc != VITX_OK) return capi_fail(rc, err);
-  if (loss_host) MIM_HIP(hipMemcpyAsync(loss_host, m->loss, 4, hipMemcpyDeviceToHost, s));
-  MIM_HIP(hipStreamSynchronize(s));
+  if (loss_host) CAPI_HIP(hipMemcpyAsync(loss_host, m->loss, 4, hipMemcpyDeviceToHost, s));
+  CAPI_HIP(hipStreamSynchronize(s));
   return VITX_OK;
-  MIM_CATCH
+  CAPI_CATCH
 }
 int32_t vitx_mim_backward(vitx_mim_handle m) {
-  MIM_TRY
+  CAPI_TRY
   if (!m) return capi_fail(VITX_ERR_INVALID, "null handle");
   std::string err;
   int rc = mim_backward(m, err);
   if (rc != VITX_OK) return capi_fail(rc, err);
   return VITX_OK;
-  MIM_CATCH
+  CAPI_CATCH
 }
 
 int32_t vitx_mim_read(vitx_mim_handle m, const char* which, float* out_host, int64_t cap, int64_t* n_elems) {
-  MIM_TRY
+  CAPI_TRY
   if (!m || !which || !out_host) return capi_fail(VITX_ERR_INVALID, "null argument");
   if (!m->have_fwd) return capi_fail(VITX_ERR_STATE, "read requires a preceding forward");
   const std::string w = which;
@@ -591,10 +512,10 @@ int32_t vitx_mim_read(vitx_mim_handle m, const char* which, float* out_host, int
   if (n_elems) *n_elems = n;
   if (n > cap) return capi_fail(VITX_ERR_INVALID, "output buffer too small");
   hipStream_t s = m->enc->stream;
-  MIM_HIP(hipMemcpyAsync(out_host, src, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-  MIM_HIP(hipStreamSynchronize(s));
+  CAPI_HIP(hipMemcpyAsync(out_host, src, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  CAPI_HIP(hipStreamSynchronize(s));
   return VITX_OK;
-  MIM_CATCH
+  CAPI_CATCH
 }
 
 }  // extern "C"

@@ -7,7 +7,7 @@
 //
 // Index convention: idx is int32 [b, ldi]; a "position range" [j0, j1) selects the columns of idx an op looks at; inv is the
 // inverse map int32 [b, n] (inv[b, idx[b, j]] = j for j in the range the inverse was built for, -1 elsewhere).
-#include "kernels.h"
+#include "composite.h"
 
 namespace {
 
@@ -197,11 +197,7 @@ __global__ void mpp_labels_kernel(const float* __restrict__ img, int H, int W, i
 }
 
 inline unsigned blocks_for(int64_t total) { return (unsigned)ceil_div(total, 256); }   // one element per thread, no grid-stride loop
-inline bool vec_ok(int d, std::initializer_list<const void*> ptrs) {
-  if (d % 4) return false;
-  for (const void* p : ptrs) if (p && ((uintptr_t)p & 15)) return false;
-  return true;
-}
+inline bool vec_ok(int d, std::initializer_list<const void*> ptrs) { return d % 4 == 0 && aligned16(ptrs); }
 
 }  // namespace
 

@@ -9,11 +9,13 @@ from typing import Dict, List, Optional
 import numpy as np
 
 from . import _native as N
-from ._model import VitxModel, _Weight, pair
+from ._composite import ParamBlob
+from ._model import VitxModel, pair
 
 
-class MimWrapper:
+class MimWrapper(ParamBlob):
     _kind = N.MIM_MAE
+    _HANDLE, _PREFIX = "_mim", "vitx_mim"
 
     def _init_mim(self, image_size, encoder: VitxModel, masking_ratio: float, *, decoder_dim=0, decoder_depth=0, decoder_heads=0,
                   decoder_dim_head=0, literal_loss=True, seed=None, mpp=None):
@@ -120,51 +122,14 @@ class MimWrapper:
                 v = np.zeros(n)
             self._blob[off:off + n] = v.astype(np.float32)
 
-    def _push_params(self):
-        if self._mim is not None:
-            N.check(N.lib().vitx_mim_set_params(self._mim, self._blob.ctypes.data_as(C.c_void_p), self._n))
-        self._device_newer = False
-
-    def _pull_params(self):
-        if self._mim is not None and self._device_newer:
-            N.check(N.lib().vitx_mim_get_params(self._mim, self._blob.ctypes.data_as(C.c_void_p), self._n))
-            self._device_newer = False
-
-    def __del__(self):
-        try:
-            if getattr(self, "_mim", None) is not None:
-                N.lib().vitx_mim_destroy(self._mim)
-                self._mim = None
-        except Exception:
-            pass
-
     def _check_live(self, what: str):
         if self._mim is None or self._enc_gen != self.encoder._handle_gen:
             raise N.VitxError(N.ERR_STATE, f"{what} requires a preceding forward (the encoder's device plan was rebuilt since)")
 
-    # ---- Keras-like surface of the wrapper's own variables
-    @property
-    def weights(self) -> List[_Weight]:
-        return [_Weight(self, n, s, o) for n, s, o in self._table]
-
-    def get_weights(self) -> List[np.ndarray]:
-        self._pull_params()
-        return [self._blob[o:o + int(np.prod(s))].reshape(s).copy() for _, s, o in self._table]
-
-    def set_weights(self, weights) -> None:
-        assert len(weights) == len(self._table), f"expected {len(self._table)} arrays, got {len(weights)}"
-        for w, (n, s, o) in zip(weights, self._table):
-            a = np.asarray(w, dtype=np.float32)
-            # the reference's own shape, or the same values without / with singleton axes (MPP's mask token is [1, 1, c p^2], mpp.py:159)
-            assert tuple(d for d in a.shape if d != 1) == tuple(d for d in s if d != 1), f"{n}: expected shape {tuple(s)}, got {a.shape}"
-            self._blob[o:o + a.size] = a.reshape(-1)
-        self._push_params()
-
-    def state_dict(self) -> Dict[str, np.ndarray]:
-        return {n: w for (n, _, _), w in zip(self._table, self.get_weights())}
-
-    def load_state_dict(self, sd: Dict[str, np.ndarray]) -> None:
-        self.set_weights([sd[n] for n, _, _ in self._table])
+    @staticmethod
+    def _shape_ok(got, want) -> bool:
+        """The reference's own shape, or the same values without / with singleton axes (MPP's mask token is [1, 1, c p^2], mpp.py:159)."""
+        return tuple(d for d in got if d != 1) == tuple(d for d in want if d != 1)
 
     def num_masked(self, H: Optional[int] = None, W: Optional[int] = None):
         """(num_patches, num_masked) at an image size: num_masked = int(masking_ratio * num_patches) (mae.py:57, simmim.py:106)."""

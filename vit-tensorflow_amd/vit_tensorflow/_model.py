@@ -5,11 +5,12 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, List, Optional, Sequence
+from typing import Optional
 
 import numpy as np
 
 from . import _native as N
+from ._composite import ParamBlob, _Weight, as_host, like  # noqa: F401  (_Weight: imported from here by the wrappers' users)
 
 
 def pair(t):
@@ -24,33 +25,6 @@ def layer_scale_init(depth_1based: int) -> float:
     if depth_1based <= 24:
         return 1e-5
     return 1e-6
-
-
-class _Weight:
-    """Minimal stand-in for a tf.Variable: `.name`, `.shape`, `.numpy()`, `.assign()`."""
-
-    def __init__(self, owner: "VitxModel", name: str, shape, offset: int):
-        self._owner, self.name, self.shape, self._offset = owner, name, tuple(shape), offset
-
-    def numpy(self) -> np.ndarray:
-        self._owner._pull_params()
-        n = int(np.prod(self.shape))
-        return self._owner._blob[self._offset:self._offset + n].reshape(self.shape).copy()
-
-    def assign(self, value) -> None:
-        v = np.asarray(value, dtype=np.float32)
-        assert v.shape == self.shape, f"shape mismatch for {self.name}: {v.shape} vs {self.shape}"
-        self._owner._pull_params()
-        self._owner._blob[self._offset:self._offset + v.size] = v.reshape(-1)
-        self._owner._push_params()
-
-    def __array__(self, dtype=None):
-        a = self.numpy()
-        return a.astype(dtype) if dtype is not None else a
-
-    def __getitem__(self, idx):
-        """`encoder.pos_embedding[:, 1:(num_patches + 1)]` (mae.py:54, simmim.py:95, distill.py:24)."""
-        return self.numpy()[idx]
 
 
 class _TransformerProxy:
@@ -153,7 +127,7 @@ class _Dropout:
         return x
 
 
-class VitxModel:
+class VitxModel(ParamBlob):
     _variant = N.VARIANT_VIT
 
     def _init_common(self, *, image_size, patch_size, num_classes, dim, depth, heads, mlp_dim, pool, dim_head, dropout,
@@ -259,23 +233,8 @@ class VitxModel:
                                      var.ctypes.data_as(C.c_void_p) if var is not None else None, self._n, C.byref(step), None, None))
         return mom, var, int(step.value)
 
-    def _push_params(self):
-        if self._handle is not None:
-            N.check(N.lib().vitx_set_params(self._handle, self._blob.ctypes.data_as(C.c_void_p), self._n))
-        self._device_newer = False
-
-    def _pull_params(self):
-        if self._handle is not None and self._device_newer:
-            N.check(N.lib().vitx_get_params(self._handle, self._blob.ctypes.data_as(C.c_void_p), self._n))
-            self._device_newer = False
-
-    def __del__(self):
-        try:
-            if getattr(self, "_handle", None) is not None and not getattr(self, "_borrowed", False):
-                N.lib().vitx_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
+    def _owns_handle(self) -> bool:
+        return not getattr(self, "_borrowed", False)   # False: the handle belongs to a wrapper object (MAE's decoder)
 
     # ---- Keras-like surface
     def build(self, input_shape=None):
@@ -285,36 +244,6 @@ class VitxModel:
             b = int(input_shape[0])
         self._ensure_handle(b)
         return self
-
-    @property
-    def weights(self) -> List[_Weight]:
-        return [_Weight(self, n, s, o) for n, s, o in self._table]
-
-    trainable_variables = weights
-    trainable_weights = weights
-
-    def get_weights(self) -> List[np.ndarray]:
-        self._pull_params()
-        return [self._blob[o:o + int(np.prod(s))].reshape(s).copy() for _, s, o in self._table]
-
-    def set_weights(self, weights: Sequence[np.ndarray]) -> None:
-        assert len(weights) == len(self._table), f"expected {len(self._table)} arrays, got {len(weights)}"
-        for w, (n, s, o) in zip(weights, self._table):
-            a = np.asarray(w, dtype=np.float32)
-            assert a.shape == tuple(s), f"{n}: expected shape {tuple(s)}, got {a.shape}"
-            self._blob[o:o + a.size] = a.reshape(-1)
-        self._push_params()
-
-    def state_dict(self) -> Dict[str, np.ndarray]:
-        return {n: w for (n, _, _), w in zip(self._table, self.get_weights())}
-
-    def load_state_dict(self, sd: Dict[str, np.ndarray]) -> None:
-        self.set_weights([sd[n] for n, _, _ in self._table])
-
-    @staticmethod
-    def _npz_path(path: str) -> str:
-        path = str(path)
-        return path if path.endswith(".npz") else path + ".npz"    # np.savez appends the suffix: both directions agree on the name
 
     def save_weights(self, path: str, format: str = "named") -> None:
         """format="named" (default): weights by engine parameter name in one .npz.  format="keras_list": the arrays of `get_weights()` in
@@ -328,7 +257,7 @@ class VitxModel:
         if format == "keras_list":
             np.savez(self._npz_path(path), *self.get_weights())
         elif format == "named":
-            np.savez(self._npz_path(path), **self.state_dict())
+            super().save_weights(path)
         else:
             raise ValueError("format must be 'named' or 'keras_list'")
 
@@ -338,8 +267,8 @@ class VitxModel:
             files = list(z.files)
             if files and all(f.startswith("arr_") and f[4:].isdigit() for f in files):
                 self.set_weights([z[f"arr_{i}"] for i in range(len(files))])     # Keras get_weights() order
-            else:
-                self.load_state_dict({k: z[k] for k in files})
+                return
+        super().load_weights(path)
 
     @property
     def pos_embedding(self):
@@ -349,23 +278,9 @@ class VitxModel:
     def cls_token(self):
         return self.weights[1]
 
-    def count_params(self) -> int:
-        return int(self._n)
-
-    # ---- tensors in / out: numpy, torch (CPU or ROCm) -- TensorFlow is what the reference used (vit.py:193)
-    @staticmethod
-    def _as_host(x):
-        is_torch = type(x).__module__.startswith("torch")
-        if is_torch:
-            return np.ascontiguousarray(x.detach().to("cpu").float().numpy()), x
-        return np.ascontiguousarray(np.asarray(x, dtype=np.float32)), None
-
-    @staticmethod
-    def _like(out: np.ndarray, proto):
-        if proto is None:
-            return out
-        import torch
-        return torch.from_numpy(out).to(proto.device)
+    # ---- tensors in / out
+    _as_host = staticmethod(as_host)
+    _like = staticmethod(like)
 
     def __call__(self, img, training=True, **kwargs):
         """ViT.call(img, training=True)  (vit.py:159; `training=True` is the reference's default)."""

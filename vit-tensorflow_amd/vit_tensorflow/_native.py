@@ -266,50 +266,40 @@ def check(rc: int) -> None:
         raise VitxError(rc, lib().vitx_last_error().decode("utf-8", "replace"))
 
 
-def param_table(cfg: Config):
-    """[(name, shape, offset)] from the C library (host-only call; no GPU needed)."""
+def table_of(prefix: str, arg):
+    """([(name, shape, offset)], elements) from `<prefix>_param_table_size / _entry`; arg: what they take first (a config by reference, or a handle)."""
     l = lib()
+    size_fn, entry_fn = getattr(l, prefix + "_param_table_size"), getattr(l, prefix + "_param_table_entry")
     nt, ne = C.c_int64(), C.c_int64()
-    check(l.vitx_param_table_size(C.byref(cfg), C.byref(nt), C.byref(ne)))
+    check(size_fn(arg, C.byref(nt), C.byref(ne)))
     out = []
     name = C.create_string_buffer(256)
     shape = (C.c_int64 * 4)()
     rank, off = C.c_int32(), C.c_int64()
     for i in range(nt.value):
-        check(l.vitx_param_table_entry(C.byref(cfg), i, name, 256, shape, C.byref(rank), C.byref(off)))
+        check(entry_fn(arg, i, name, 256, shape, C.byref(rank), C.byref(off)))
         out.append((name.value.decode(), tuple(int(shape[k]) for k in range(rank.value)), int(off.value)))
     return out, int(ne.value)
+
+
+def param_table(cfg: Config):
+    """[(name, shape, offset)] from the C library (host-only call; no GPU needed)."""
+    return table_of("vitx", C.byref(cfg))
 
 
 def crossvit_param_table(cfg: CrossViTConfig):
     """[(name, shape, offset)] of CrossViT's variables from the C library (host-only call; no GPU needed)."""
-    l = lib()
-    nt, ne = C.c_int64(), C.c_int64()
-    check(l.vitx_crossvit_param_table_size(C.byref(cfg), C.byref(nt), C.byref(ne)))
-    out = []
-    name = C.create_string_buffer(256)
-    shape = (C.c_int64 * 4)()
-    rank, off = C.c_int32(), C.c_int64()
-    for i in range(nt.value):
-        check(l.vitx_crossvit_param_table_entry(C.byref(cfg), i, name, 256, shape, C.byref(rank), C.byref(off)))
-        out.append((name.value.decode(), tuple(int(shape[k]) for k in range(rank.value)), int(off.value)))
-    return out, int(ne.value)
+    return table_of("vitx_crossvit", C.byref(cfg))
+
+
+def cct_param_table(cfg: CCTConfig):
+    """[(name, shape, offset)] of CCT's variables from the C library (host-only call; no GPU needed)."""
+    return table_of("vitx_cct", C.byref(cfg))
 
 
 def mim_param_table(handle, prefix="vitx_mim"):
     """[(name, shape, offset)] of a wrapper object's own parameters (prefix 'vitx_mim': MAE / SimMIM, 'vitx_distill': DistillWrapper)."""
-    l = lib()
-    size_fn, entry_fn = getattr(l, prefix + "_param_table_size"), getattr(l, prefix + "_param_table_entry")
-    nt, ne = C.c_int64(), C.c_int64()
-    check(size_fn(handle, C.byref(nt), C.byref(ne)))
-    out = []
-    name = C.create_string_buffer(256)
-    shape = (C.c_int64 * 4)()
-    rank, off = C.c_int32(), C.c_int64()
-    for i in range(nt.value):
-        check(entry_fn(handle, i, name, 256, shape, C.byref(rank), C.byref(off)))
-        out.append((name.value.decode(), tuple(int(shape[k]) for k in range(rank.value)), int(off.value)))
-    return out, int(ne.value)
+    return table_of(prefix, handle)
 
 
 def debug_switches():
@@ -320,21 +310,6 @@ def debug_switches():
     buf = C.create_string_buffer(need.value)
     check(lib().vitx_debug_switches(buf, need.value, None))
     return [tuple(line.split("\t", 3)) for line in buf.value.decode().splitlines()]
-
-
-def cct_param_table(cfg: CCTConfig):
-    """[(name, shape, offset)] of CCT's variables from the C library (host-only call; no GPU needed)."""
-    l = lib()
-    nt, ne = C.c_int64(), C.c_int64()
-    check(l.vitx_cct_param_table_size(C.byref(cfg), C.byref(nt), C.byref(ne)))
-    out = []
-    name = C.create_string_buffer(256)
-    shape = (C.c_int64 * 4)()
-    rank, off = C.c_int32(), C.c_int64()
-    for i in range(nt.value):
-        check(l.vitx_cct_param_table_entry(C.byref(cfg), i, name, 256, shape, C.byref(rank), C.byref(off)))
-        out.append((name.value.decode(), tuple(int(shape[k]) for k in range(rank.value)), int(off.value)))
-    return out, int(ne.value)
 
 
 def cct_sequence_length(cfg: CCTConfig) -> int:

@@ -10,12 +10,11 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, List, Sequence
 
 import numpy as np
 
 from . import _native as N
-from ._model import VitxModel, _Weight
+from ._composite import NativeComposite, as_host, like
 
 
 def pair(t):
@@ -73,7 +72,9 @@ def sequence_length(img_size, n_conv_layers=1, stride=2, pooling_stride=2) -> in
     return h * w
 
 
-class CCT:
+class CCT(NativeComposite):
+    _PREFIX, _NAME = "vitx_cct", "CCT"
+
     def __init__(self, img_size=224, embedding_dim=768, n_input_channels=3, n_conv_layers=1, kernel_size=7, stride=2, pooling_kernel_size=3,
                  pooling_stride=2, *args, **kwargs):
         """Same arguments as the reference: the eight above (cct.py:308-317) and, through **kwargs, TransformerClassifier's num_layers=12,
@@ -153,102 +154,14 @@ class CCT:
                 v = np.zeros(n)
             self._blob[off:off + n] = v.astype(np.float32)
 
-    # ---- handle management (rebuilt, weights kept, when a larger batch arrives)
-    def _ensure_handle(self, batch: int):
-        l = N.lib()
-        if self._handle is not None and batch <= self._cfg.max_batch:
-            return self._handle
-        if self._handle is not None:
-            self._pull_params()
-            N.check(l.vitx_cct_destroy(self._handle))
-            self._handle = None
-        self._cfg.max_batch = max(int(batch), int(self._cfg.max_batch))
-        h = C.c_void_p()
-        N.check(l.vitx_cct_create(C.byref(self._cfg), C.byref(h)))
-        self._handle = h
-        self._push_params()
-        return h
-
-    def _push_params(self):
-        if self._handle is not None:
-            N.check(N.lib().vitx_cct_set_params(self._handle, self._blob.ctypes.data_as(C.c_void_p), self._n))
-        self._device_newer = False
-
-    def _pull_params(self):
-        if self._handle is not None and self._device_newer:
-            N.check(N.lib().vitx_cct_get_params(self._handle, self._blob.ctypes.data_as(C.c_void_p), self._n))
-            self._device_newer = False
-
-    def params_changed(self):
-        """The device parameter arena (params_dev) was written by an optimizer outside the library."""
-        if self._handle is not None:
-            N.check(N.lib().vitx_cct_params_changed(self._handle))
-            self._device_newer = True
-
-    def params_dev(self):
-        """(device pointer, elements) of the fp32 parameter arena (table order, every tensor 16-B aligned)."""
-        p, n = C.c_void_p(), C.c_int64()
-        N.check(N.lib().vitx_cct_params_dev(self._ensure_handle(1), C.byref(p), C.byref(n)))
-        return p.value, n.value
-
-    def grads_dev(self):
-        p, n = C.c_void_p(), C.c_int64()
-        N.check(N.lib().vitx_cct_grads_dev(self._ensure_handle(1), C.byref(p), C.byref(n)))
-        return p.value, n.value
-
-    def __del__(self):
-        try:
-            if getattr(self, "_handle", None) is not None:
-                N.lib().vitx_cct_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
-
-    # ---- Keras-like surface
-    @property
-    def weights(self) -> List[_Weight]:
-        return [_Weight(self, n, s, o) for n, s, o in self._table]
-
-    trainable_variables = weights
-    trainable_weights = weights
-
-    def get_weights(self) -> List[np.ndarray]:
-        self._pull_params()
-        return [self._blob[o:o + int(np.prod(s))].reshape(s).copy() for _, s, o in self._table]
-
-    def set_weights(self, weights: Sequence[np.ndarray]) -> None:
-        assert len(weights) == len(self._table), f"expected {len(self._table)} arrays, got {len(weights)}"
-        for w, (n, s, o) in zip(weights, self._table):
-            a = np.asarray(w, dtype=np.float32)
-            assert a.shape == tuple(s), f"{n}: expected shape {tuple(s)}, got {a.shape}"
-            self._blob[o:o + a.size] = a.reshape(-1)
-        self._push_params()
-
-    def state_dict(self) -> Dict[str, np.ndarray]:
-        return {n: w for (n, _, _), w in zip(self._table, self.get_weights())}
-
-    def load_state_dict(self, sd: Dict[str, np.ndarray]) -> None:
-        self.set_weights([sd[n] for n, _, _ in self._table])
-
-    def save_weights(self, path: str) -> None:
-        """Weights by table name in one .npz."""
-        np.savez(VitxModel._npz_path(path), **self.state_dict())
-
-    def load_weights(self, path: str) -> None:
-        with np.load(VitxModel._npz_path(path)) as z:
-            self.load_state_dict({k: z[k] for k in z.files})
-
-    def count_params(self) -> int:
-        return int(self._n)
-
-    # ---- forward / backward
+    # ---- forward
     def __call__(self, img, training=None, **kwargs):
         """CCT.call(img, training=None) (cct.py:342-345).  img: NHWC numpy or torch of exactly the constructed img_size."""
         if training:
             raise NotImplementedError("CCT(training=True) needs dropout on the attention probabilities (rate 0.1, cct.py:132) and per-sample "
                                       "stochastic depth (rates up to 0.1, cct.py:74-91,161,170); neither is built.  Only the deterministic path "
                                       "(training falsy) is supported.")
-        x, proto = VitxModel._as_host(img)
+        x, proto = as_host(img)
         if x.ndim != 4 or x.shape[3] != self.n_input_channels:
             raise ValueError(f"expected NHWC images [b, H, W, {self.n_input_channels}]")
         b, H, W, _c = x.shape
@@ -259,21 +172,10 @@ class CCT:
         self._img_shape = (b, H, W, self.n_input_channels)
         out = np.empty((b, self.num_classes), dtype=np.float32)
         N.check(N.lib().vitx_cct_forward(h, x.ctypes.data_as(C.c_void_p), b, out.ctypes.data_as(C.c_void_p)))
-        return VitxModel._like(out, proto)
+        return like(out, proto)
 
     call = __call__
     predict = lambda self, img, **kw: self(img, training=False, **kw)
-
-    def backward(self, dlogits, want_dimg: bool = False):
-        """VJP of the last forward.  Returns ({name: grad}, dimg | None)."""
-        if self._handle is None:
-            raise N.VitxError(N.ERR_STATE, "backward requires a preceding forward")
-        d, _ = VitxModel._as_host(dlogits)
-        dimg = np.empty(self._img_shape, dtype=np.float32) if want_dimg else None
-        N.check(N.lib().vitx_cct_backward(self._handle, d.ctypes.data_as(C.c_void_p), dimg.ctypes.data_as(C.c_void_p) if want_dimg else None))
-        g = np.empty(self._n, dtype=np.float32)
-        N.check(N.lib().vitx_cct_get_grads(self._handle, g.ctypes.data_as(C.c_void_p), self._n))
-        return {n: g[o:o + int(np.prod(s))].reshape(s) for n, s, o in self._table}, dimg
 
     def read(self, which: str) -> np.ndarray:
         """Tensors of the last forward for bisecting: 'tokens' / 'encoded' [b, n, dim], 'pool_weights' [b, n], 'pooled' [b, dim]."""
@@ -286,14 +188,4 @@ class CCT:
         out = buf[:n.value]
         return out.reshape(b, -1, self.embedding_dim) if which in ("tokens", "encoded") else out.reshape(b, -1)
 
-    # ---- not provided for CCT: refuse instead of misbehaving
-    def comm_init(self, *a, **k):
-        raise NotImplementedError("CCT: data parallel is not supported (all-reduce grads_dev() outside the library)")
-
-    def optimizer_step(self, *a, **k):
-        raise NotImplementedError("CCT: no in-library optimizer step (update params_dev() outside the library, then params_changed())")
-
-    apply_gradients = optimizer_step
-
-    def capture_graph(self, *a, **k):
-        raise NotImplementedError("CCT: HIP graph capture is not supported")
+    apply_gradients = NativeComposite.optimizer_step

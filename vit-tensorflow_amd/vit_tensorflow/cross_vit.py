@@ -5,15 +5,16 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, List, Sequence
 
 import numpy as np
 
 from . import _native as N
-from ._model import VitxModel, _Weight
+from ._composite import NativeComposite, as_host, like
 
 
-class CrossViT:
+class CrossViT(NativeComposite):
+    _PREFIX, _NAME = "vitx_crossvit", "CrossViT"
+
     def __init__(self, image_size, num_classes, sm_dim, lg_dim, sm_patch_size=12, sm_enc_depth=1, sm_enc_heads=8, sm_enc_mlp_dim=2048,
                  sm_enc_dim_head=64, lg_patch_size=16, lg_enc_depth=4, lg_enc_heads=8, lg_enc_mlp_dim=2048, lg_enc_dim_head=64,
                  cross_attn_depth=2, cross_attn_heads=8, cross_attn_dim_head=64, depth=3, dropout=0.1, emb_dropout=0.1,
@@ -61,99 +62,11 @@ class CrossViT:
                 v = np.zeros(n)
             self._blob[off:off + n] = v.astype(np.float32)
 
-    # ---- handle management (rebuilt, weights kept, when a larger batch arrives)
-    def _ensure_handle(self, batch: int):
-        l = N.lib()
-        if self._handle is not None and batch <= self._cfg.max_batch:
-            return self._handle
-        if self._handle is not None:
-            self._pull_params()
-            N.check(l.vitx_crossvit_destroy(self._handle))
-            self._handle = None
-        self._cfg.max_batch = max(int(batch), int(self._cfg.max_batch))
-        h = C.c_void_p()
-        N.check(l.vitx_crossvit_create(C.byref(self._cfg), C.byref(h)))
-        self._handle = h
-        self._push_params()
-        return h
-
-    def _push_params(self):
-        if self._handle is not None:
-            N.check(N.lib().vitx_crossvit_set_params(self._handle, self._blob.ctypes.data_as(C.c_void_p), self._n))
-        self._device_newer = False
-
-    def _pull_params(self):
-        if self._handle is not None and self._device_newer:
-            N.check(N.lib().vitx_crossvit_get_params(self._handle, self._blob.ctypes.data_as(C.c_void_p), self._n))
-            self._device_newer = False
-
-    def params_changed(self):
-        """The device parameter arena (params_dev) was written by an optimizer outside the library."""
-        if self._handle is not None:
-            N.check(N.lib().vitx_crossvit_params_changed(self._handle))
-            self._device_newer = True
-
-    def params_dev(self):
-        """(device pointer, elements) of the fp32 parameter arena (table order, every tensor 16-B aligned)."""
-        p, n = C.c_void_p(), C.c_int64()
-        N.check(N.lib().vitx_crossvit_params_dev(self._ensure_handle(1), C.byref(p), C.byref(n)))
-        return p.value, n.value
-
-    def grads_dev(self):
-        p, n = C.c_void_p(), C.c_int64()
-        N.check(N.lib().vitx_crossvit_grads_dev(self._ensure_handle(1), C.byref(p), C.byref(n)))
-        return p.value, n.value
-
-    def __del__(self):
-        try:
-            if getattr(self, "_handle", None) is not None:
-                N.lib().vitx_crossvit_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
-
-    # ---- Keras-like surface
-    @property
-    def weights(self) -> List[_Weight]:
-        return [_Weight(self, n, s, o) for n, s, o in self._table]
-
-    trainable_variables = weights
-    trainable_weights = weights
-
-    def get_weights(self) -> List[np.ndarray]:
-        self._pull_params()
-        return [self._blob[o:o + int(np.prod(s))].reshape(s).copy() for _, s, o in self._table]
-
-    def set_weights(self, weights: Sequence[np.ndarray]) -> None:
-        assert len(weights) == len(self._table), f"expected {len(self._table)} arrays, got {len(weights)}"
-        for w, (n, s, o) in zip(weights, self._table):
-            a = np.asarray(w, dtype=np.float32)
-            assert a.shape == tuple(s), f"{n}: expected shape {tuple(s)}, got {a.shape}"
-            self._blob[o:o + a.size] = a.reshape(-1)
-        self._push_params()
-
-    def state_dict(self) -> Dict[str, np.ndarray]:
-        return {n: w for (n, _, _), w in zip(self._table, self.get_weights())}
-
-    def load_state_dict(self, sd: Dict[str, np.ndarray]) -> None:
-        self.set_weights([sd[n] for n, _, _ in self._table])
-
-    def save_weights(self, path: str) -> None:
-        """Weights by table name in one .npz."""
-        np.savez(VitxModel._npz_path(path), **self.state_dict())
-
-    def load_weights(self, path: str) -> None:
-        with np.load(VitxModel._npz_path(path)) as z:
-            self.load_state_dict({k: z[k] for k in z.files})
-
-    def count_params(self) -> int:
-        return int(self._n)
-
-    # ---- forward / backward
+    # ---- forward
     def __call__(self, img, training=True, seed=None, **_):
         """CrossViT.call(img, training=True) (cross_vit.py:290).  img: NHWC numpy or torch; H and W at most image_size and divisible
         by both patch sizes (the position embeddings are sliced, cross_vit.py:226)."""
-        x, proto = VitxModel._as_host(img)
+        x, proto = as_host(img)
         assert x.ndim == 4 and x.shape[3] == 3, "expected NHWC images [b, H, W, 3]"
         b, H, W, _ = x.shape
         for p in (self.sm_patch_size, self.lg_patch_size):
@@ -164,22 +77,10 @@ class CrossViT:
         seed = int(np.random.randint(0, 2 ** 31 - 1)) if seed is None else int(seed)
         N.check(N.lib().vitx_crossvit_forward(h, x.ctypes.data_as(C.c_void_p), b, H, W, 1 if training else 0, seed,
                                               out.ctypes.data_as(C.c_void_p)))
-        return VitxModel._like(out, proto)
+        return like(out, proto)
 
     call = __call__
     predict = lambda self, img, **kw: self(img, training=False, **kw)
-
-    def backward(self, dlogits, want_dimg: bool = False):
-        """VJP of the last forward.  Returns ({name: grad}, dimg | None)."""
-        if self._handle is None:
-            raise N.VitxError(N.ERR_STATE, "backward requires a preceding forward")
-        d, _ = VitxModel._as_host(dlogits)
-        dimg = np.empty(self._img_shape, dtype=np.float32) if want_dimg else None
-        N.check(N.lib().vitx_crossvit_backward(self._handle, d.ctypes.data_as(C.c_void_p),
-                                               dimg.ctypes.data_as(C.c_void_p) if want_dimg else None))
-        g = np.empty(self._n, dtype=np.float32)
-        N.check(N.lib().vitx_crossvit_get_grads(self._handle, g.ctypes.data_as(C.c_void_p), self._n))
-        return {n: g[o:o + int(np.prod(s))].reshape(s) for n, s, o in self._table}, dimg
 
     def read(self, which: str) -> np.ndarray:
         """Tensors of the last forward for bisecting: 'sm_tokens' / 'lg_tokens' [b, n, dim], 'sm_logits' / 'lg_logits' [b, num_classes]."""
@@ -195,13 +96,3 @@ class CrossViT:
             return out.reshape(b, self.num_classes)
         dim = self._cfg.sm_dim if which.startswith("sm") else self._cfg.lg_dim
         return out.reshape(b, -1, dim)
-
-    # ---- not provided for CrossViT: refuse instead of misbehaving
-    def comm_init(self, *a, **k):
-        raise NotImplementedError("CrossViT: data parallel is not supported (all-reduce grads_dev() outside the library)")
-
-    def optimizer_step(self, *a, **k):
-        raise NotImplementedError("CrossViT: no in-library optimizer step (update params_dev() outside the library, then params_changed())")
-
-    def capture_graph(self, *a, **k):
-        raise NotImplementedError("CrossViT: HIP graph capture is not supported")

@@ -10,7 +10,8 @@ from typing import Dict, List, Optional
 import numpy as np
 
 from . import _native as N
-from ._model import VitxModel, _Weight
+from ._composite import ParamBlob
+from ._model import VitxModel
 from .t2t import T2TViT
 from .vit import ViT
 
@@ -145,7 +146,9 @@ class DistillableEfficientViT:
     call = __call__
 
 
-class DistillWrapper:
+class DistillWrapper(ParamBlob):
+    _HANDLE, _PREFIX = "_h", "vitx_distill"
+
     def __init__(self, teacher, student, temperature=1.0, alpha=0.5, hard=False, *, literal_loss=True, seed=None):
         """Same arguments as the reference (distill.py:88).  Engine-only keyword extras: literal_loss (soft mode) -- True keeps
         the distillation term exactly as distill.py:122-129 computes it (Keras' KLDivergence clips the LOG-probabilities it is
@@ -209,46 +212,12 @@ class DistillWrapper:
                 v = np.zeros(n)
             self._blob[off:off + n] = v.astype(np.float32)
 
-    def _push_params(self):
-        if self._h is not None:
-            N.check(N.lib().vitx_distill_set_params(self._h, self._blob.ctypes.data_as(C.c_void_p), self._n))
-        self._device_newer = False
-
     def _pull_params(self):
         pass   # the wrapper's variables only change through set_weights / assign (host side)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None:
-                N.lib().vitx_distill_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    @property
-    def weights(self) -> List[_Weight]:
-        return [_Weight(self, n, s, o) for n, s, o in self._table]
 
     @property
     def distillation_token(self):
         return self.weights[0]
-
-    def get_weights(self) -> List[np.ndarray]:
-        return [self._blob[o:o + int(np.prod(s))].reshape(s).copy() for _, s, o in self._table]
-
-    def set_weights(self, weights) -> None:
-        assert len(weights) == len(self._table), f"expected {len(self._table)} arrays, got {len(weights)}"
-        for w, (n, s, o) in zip(weights, self._table):
-            a = np.asarray(w, dtype=np.float32)
-            assert a.shape == tuple(s), f"{n}: expected shape {tuple(s)}, got {a.shape}"
-            self._blob[o:o + a.size] = a.reshape(-1)
-        self._push_params()
-
-    def state_dict(self) -> Dict[str, np.ndarray]:
-        return {n: w for (n, _, _), w in zip(self._table, self.get_weights())}
-
-    def load_state_dict(self, sd) -> None:
-        self.set_weights([sd[n] for n, _, _ in self._table])
 
     def __call__(self, inputs, temperature=None, alpha=None, training=True, **kwargs):
         """DistillWrapper.call((img, labels), temperature, alpha, training) (distill.py:107): the per-image loss [b]."""
