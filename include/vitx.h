@@ -81,7 +81,15 @@ typedef struct vitx_config {
    * small_dataset == 0 and dropout == 0.  Such a handle serves vitx_cct_* through the device-pointer transformer entry; its image entry points
    * return VITX_ERR_UNSUPPORTED.  0 (a zeroed struct) = off: the handle is exactly the ordinary one. */
   int32_t cct_block;
-  int32_t reserved[3];
+  /* nest.Transformer (nest.py:77-148) run on (b * blocks^2) independent sequences: != 0 keeps to_out for heads == 1 with dim_head == dim
+   * (nest.py:88-91 always projects) and runs the plain-softmax form of the small-head attention kernels (attn_lsa.hip without mask and
+   * temperature) for dim_head in {16, 32} and at most 288 tokens; dim_head 64 keeps the fused kernels, everything else the materialised path.
+   * The parameter table is the ordinary ViT's.  Needs variant VITX_VARIANT_VIT, num_parallel_branches <= 1, small_dataset == 0 and
+   * cct_block == 0.  Such a handle serves vitx_nest_* through the device-pointer transformer entry; its image entry points return
+   * VITX_ERR_UNSUPPORTED.  0 (a zeroed struct) = off: the handle is exactly the ordinary one.  Whether the small-head kernels run is the
+   * composite's choice per handle (vitx_nest_config.small_attn). */
+  int32_t nest_block;
+  int32_t reserved[2];
 } vitx_config;
 
 typedef struct vitx_engine* vitx_handle;
@@ -484,6 +492,54 @@ int32_t vitx_cct_profile_begin(vitx_cct_handle m);
 int32_t vitx_cct_profile_end(vitx_cct_handle m, vitx_kernel_stat* out, int32_t cap, int32_t* n_out);
 /* "tokens" [b, n, dim] (the tokenizer's output), "encoded" [b, n, dim] (after the final norm), "pool_weights" [b, n], "pooled" [b, dim] */
 int32_t vitx_cct_read(vitx_cct_handle m, const char* which, float* out_host, int64_t cap_elems, int64_t* n_elems);
+
+/* ---- NesT (nest.py:150-216): patch embedding (Rearrange + 1x1 Conv2D = Dense, :178-181), then per hierarchy level the block partition
+ * (:209) with the positional add (:140-142), block_repeats[i] transformer blocks on (b * blocks^2) sequences (one vitx_config.nest_block
+ * engine per level), the inverse partition (:211) and, except at the last level, Aggregate (:111-123): Conv2D 3x3 'SAME' with bias, channel
+ * LayerNorm, MaxPool2D 3/2 'SAME'; then LayerNorm, mean over the map, Dense (:196-200).  A handle of its own; parameter order in DESIGN.md
+ * section 20.  Only the deterministic path (dropout 0) exists. */
+typedef struct vitx_nest_config {
+  int32_t image_size, patch_size, num_classes, dim, heads, num_hierarchies;   /* nest.py:151-157 */
+  int32_t block_repeats[8];        /* cast_tuple(block_repeats, num_hierarchies), finest level first (nest.py:183); num_hierarchies <= 8 */
+  int32_t mlp_mult;                /* nest.py:159 */
+  float ln_eps;                    /* <= 0: nest.py:29's 1e-5 */
+  int32_t compute;                 /* VITX_COMPUTE_*: the transformer blocks' mode; embedding, aggregation and head keep fp32 storage */
+  int32_t max_batch;               /* images; level i's engine holds max_batch * 4^(H-1-i) sequences */
+  int32_t device_id;
+  int32_t conv_chunk;              /* images per im2col + GEMM pass of an aggregation; <= 0: sized from a fixed workspace budget */
+  /* the plain small-head attention kernels (dim_head 16 / 32, <= 288 tokens).  0: where they measured faster than the materialised path at
+   * the usage shape -- the BF16 mode (MFMA form); FP32_PARITY and BF16X3 (fp32 FMA form) keep the materialised path, which measured faster
+   * there.  1: wherever they apply.  -1: nowhere. */
+  int32_t small_attn;
+  int32_t reserved[7];
+} vitx_nest_config;
+typedef struct vitx_nest* vitx_nest_handle;
+/* host only, no GPU needed */
+int32_t vitx_nest_param_table_size(const vitx_nest_config* cfg, int64_t* n_tensors, int64_t* n_elems);
+int32_t vitx_nest_param_table_entry(const vitx_nest_config* cfg, int64_t index, char* name, int32_t name_cap, int64_t shape[4], int32_t* rank,
+                                    int64_t* offset_elems);
+int32_t vitx_nest_create(const vitx_nest_config* cfg, vitx_nest_handle* out);
+int32_t vitx_nest_destroy(vitx_nest_handle m);
+int32_t vitx_nest_set_params(vitx_nest_handle m, const float* host_blob, int64_t n_elems);
+int32_t vitx_nest_get_params(vitx_nest_handle m, float* host_blob, int64_t n_elems);
+int32_t vitx_nest_get_grads(vitx_nest_handle m, float* host_blob, int64_t n_elems);
+int32_t vitx_nest_params_dev(vitx_nest_handle m, float** dev_ptr, int64_t* n_elems);
+int32_t vitx_nest_grads_dev(vitx_nest_handle m, float** dev_ptr, int64_t* n_elems);
+int32_t vitx_nest_params_changed(vitx_nest_handle m);
+/* img [b, image_size, image_size, 3] NHWC; logits [b, num_classes] */
+int32_t vitx_nest_forward(vitx_nest_handle m, const float* img_host, int32_t b, float* logits_host);
+int32_t vitx_nest_forward_dev(vitx_nest_handle m, const float* img_dev, int32_t b, float* logits_dev_or_null);
+/* VJP of the last forward for d(logits): overwrites the gradient arena; d(img) only when asked for */
+int32_t vitx_nest_backward(vitx_nest_handle m, const float* dlogits_host, float* dimg_host_or_null);
+int32_t vitx_nest_backward_dev(vitx_nest_handle m, const float* dlogits_dev, float* dimg_dev_or_null);
+/* per-kernel-class timing of the steps between the two calls, as vitx_profile_begin / _end: every level's block classes (attn_small_fwd /
+ * _bwd among them) plus the composite's own (nest_embed, nest_blocks, nest_im2col, nest_conv_gemm, nest_col2im, nest_maxpool_fwd / _bwd,
+ * nest_head) */
+int32_t vitx_nest_profile_begin(vitx_nest_handle m);
+int32_t vitx_nest_profile_end(vitx_nest_handle m, vitx_kernel_stat* out, int32_t cap, int32_t* n_out);
+/* "embedded" [b, f, f, dim]; "level.<i>" [b, f_i, f_i, d_i] (the level's output after un-blocking, before aggregation); "aggregated.<i>"
+ * [b, f_{i+1}, f_{i+1}, d_{i+1}]; "pooled" [b, d_last] */
+int32_t vitx_nest_read(vitx_nest_handle m, const char* which, float* out_host, int64_t cap_elems, int64_t* n_elems);
 
 #ifdef __cplusplus
 }

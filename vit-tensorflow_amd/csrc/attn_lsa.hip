@@ -70,9 +70,9 @@ __device__ __forceinline__ void lsa_row_times_staged(const float* wrow, int npad
   }
 }
 
-template <typename T, int DH, int R>
+template <typename T, int DH, int R, bool PLAIN>
 __global__ __launch_bounds__(256) void attn_lsa_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ o, float* __restrict__ lse,
-                                                           const float* __restrict__ temperature, int n, int h) {
+                                                           const float* __restrict__ temperature, float scale, int n, int h) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int L = lsa_pitch<T, DH>();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void attn_lsa_fwd_kernel(const T* __restrict__
   const T* base = qkv + (int64_t)bi * n * ld + hi * DH;
   lsa_stage<T, DH>(base + inner, ld, n, Ks);
   lsa_stage<T, DH>(base + 2 * inner, ld, n, Vs);
-  const float et = expf(temperature[0]);
+  const float et = PLAIN ? scale : expf(temperature[0]);
   __syncthreads();
   for (int g = 0; g < LSA_ROWS / R; ++g) {
     const int r0 = q0 + wave * LSA_ROWS + g * R;
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void attn_lsa_fwd_kernel(const T* __restrict__
         }
       }
 #pragma unroll
-      for (int r = 0; r < R; ++r) s[r][jc] = j >= n ? -INFINITY : (j == r0 + r ? -FLT_MAX : acc[r] * et);
+      for (int r = 0; r < R; ++r) s[r][jc] = j >= n ? -INFINITY : (!PLAIN && j == r0 + r ? -FLT_MAX : acc[r] * et);
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void attn_lsa_fwd_kernel(const T* __restrict__
 #pragma unroll
       for (int jc = 0; jc < LSA_NCH; ++jc) {
         const int j = jc * 64 + lane;
-        s[r][jc] = (j < n && j != r0 + r) ? expf(s[r][jc] - m) : 0.f;   // the masked entry is exactly 0
+        s[r][jc] = (j < n && (PLAIN || j != r0 + r)) ? expf(s[r][jc] - m) : 0.f;   // the masked entry is exactly 0
         sum += s[r][jc];
       }
       sum = wave_sum(sum);
@@ -161,9 +161,9 @@ __global__ __launch_bounds__(256) void attn_lsa_fwd_kernel(const T* __restrict__
 // and C[row 4 (l >> 4) + r][col l & 15].  S tile by tile stays in registers (18 tiles x 4 fp32 at n = 288); row maxima / sums are reduced over
 // the 16 lanes of a row group; P goes through a per-wave LDS tile as bf16 (un-normalised, the fp32 row sum divides the output) to become the
 // A operand of P v.
-template <int DH>
+template <int DH, bool PLAIN>
 __global__ __launch_bounds__(256) void attn_lsa_fwd_mfma_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o, float* __restrict__ lse,
-                                                                const float* __restrict__ temperature, int n, int h) {
+                                                                const float* __restrict__ temperature, float scale, int n, int h) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int DHP = DH < 32 ? 32 : DH, KP = DHP + 8, KS = DHP / 32, NT = (LSA_N_MAX + 15) / 16;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, lg = lane >> 4;
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(256) void attn_lsa_fwd_mfma_kernel(const bf16_t* __
       if (kk < DH) qf[ks] = *(const bf16x8*)(qrow + kk);
     }
   }
-  const float et = expf(temperature[0]);
+  const float et = PLAIN ? scale : expf(temperature[0]);
   __syncthreads();
   f32x4 s[NT];
 #pragma unroll
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void attn_lsa_fwd_mfma_kernel(const bf16_t* __
 #pragma unroll
     for (int jt = 0; jt < NT; ++jt) {
       const int j = jt * 16 + lr;
-      const float v = (j < n && j != row) ? s[jt][r] * et : -INFINITY;
+      const float v = (j < n && (PLAIN || j != row)) ? s[jt][r] * et : -INFINITY;
       s[jt][r] = v;
       m = fmaxf(m, v);
     }
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256) void attn_lsa_fwd_mfma_kernel(const bf16_t* __
 #pragma unroll
     for (int jt = 0; jt < NT; ++jt) {
       const int j = jt * 16 + lr;
-      const float p = (j < n && j != row) ? expf(s[jt][r] - m) : 0.f;   // the masked entry is exactly 0
+      const float p = (j < n && (PLAIN || j != row)) ? expf(s[jt][r] - m) : 0.f;   // the masked entry is exactly 0
       sum += p;
       if (jt * 16 < n32) Ps[(4 * lg + r) * PP + j] = (bf16_t)p;        // (columns [n, n32) are written as zeros)
     }
@@ -255,21 +255,22 @@ template <int DH> size_t lsa_fwd_mfma_lds(int n) {
   const int DHP = DH < 32 ? 32 : DH, n16 = (n + 15) & ~15, PP = ((n + 31) & ~31) + 8;
   return ((size_t)n16 * (DHP + 8) + (size_t)DH * PP + (size_t)LSA_WAVES * 16 * PP) * 2;
 }
-template <int DH>
-void lsa_fwd_mfma_launch(const bf16_t* qkv, bf16_t* o, float* lse, int b, int n, int h, const float* t, hipStream_t s) {
-  auto kern = attn_lsa_fwd_mfma_kernel<DH>;
+template <int DH, bool PLAIN>
+void lsa_fwd_mfma_launch(const bf16_t* qkv, bf16_t* o, float* lse, int b, int n, int h, const float* t, float scale, hipStream_t s) {
+  auto kern = attn_lsa_fwd_mfma_kernel<DH, PLAIN>;
   vitx_set_max_smem((const void*)kern, LSA_LDS_MAX);
   const size_t lds = lsa_fwd_mfma_lds<DH>(n);
-  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, lse, t, n, h);
+  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, lse, t, scale, n, h);
 }
 
 // KEYS = false: the tile's rows are queries, K and V are staged: d(q), the row sums D = dO . o (kept in dsum for the other pass) and this workgroup's
 //               partial of the temperature gradient.
 // KEYS = true:  the tile's rows are keys, Q and dO are staged: d(k) and d(v).
-template <typename T, int DH, int R, bool KEYS>
+template <typename T, int DH, int R, bool KEYS, bool PLAIN>
 __global__ __launch_bounds__(256) void attn_lsa_bwd_kernel(const T* __restrict__ qkv, const T* __restrict__ o, const T* __restrict__ d_o,
                                                            const float* __restrict__ lse, float* __restrict__ dsum, T* __restrict__ dqkv,
-                                                           const float* __restrict__ temperature, float* __restrict__ dt_part, int n, int h) {
+                                                           const float* __restrict__ temperature, float scale, float* __restrict__ dt_part, int n,
+                                                           int h) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ float dt_wave[LSA_WAVES];
   constexpr int L = lsa_pitch<T, DH>();
@@ -296,7 +297,7 @@ __global__ __launch_bounds__(256) void attn_lsa_bwd_kernel(const T* __restrict__
     lsa_stage<T, DH>(base + inner, ld, n, As);
     lsa_stage<T, DH>(base + 2 * inner, ld, n, Bs);
   }
-  const float et = expf(temperature[0]);
+  const float et = PLAIN ? scale : expf(temperature[0]);
   float dt_acc = 0.f;
   __syncthreads();
   for (int g = 0; g < LSA_ROWS / R; ++g) {
@@ -346,11 +347,11 @@ __global__ __launch_bounds__(256) void attn_lsa_bwd_kernel(const T* __restrict__
         const float lj = KEYS ? lse_h[jj] : 0.f, Dj = KEYS ? dsum_h[jj] : 0.f;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-          const bool live = j < n && j != r0 + r && r0 + r < n;
+          const bool live = j < n && (PLAIN || j != r0 + r) && r0 + r < n;
           const float sc = sa[r] * et;
           const float p = live ? expf(sc - (KEYS ? lj : lrow[r])) : 0.f;
           const float ds = p * (sb[r] - (KEYS ? Dj : Drow[r]));
-          if (!KEYS && live) dt_acc = fmaf(ds, sc, dt_acc);
+          if (!KEYS && !PLAIN && live) dt_acc = fmaf(ds, sc, dt_acc);
           if (j < npad) { dw[r * npad + j] = ds * et; if (KEYS) pw[r * npad + j] = p; }
         }
       }
@@ -373,7 +374,7 @@ __global__ __launch_bounds__(256) void attn_lsa_bwd_kernel(const T* __restrict__
     }
     __syncthreads();
   }
-  if (!KEYS) {
+  if (!KEYS && !PLAIN) {
     dt_acc = wave_sum(dt_acc);
     if (lane == 0) dt_wave[wave] = dt_acc;
     __syncthreads();
@@ -404,11 +405,12 @@ __device__ __forceinline__ void lsa_stage_chunk(const bf16_t* __restrict__ src, 
     }
   }
 }
-template <int DH, bool KEYS>
+template <int DH, bool KEYS, bool PLAIN>
 __global__ __launch_bounds__(256) void attn_lsa_bwd_mfma_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
                                                                 const bf16_t* __restrict__ d_o, const float* __restrict__ lse,
                                                                 float* __restrict__ dsum, bf16_t* __restrict__ dqkv,
-                                                                const float* __restrict__ temperature, float* __restrict__ dt_part, int n, int h) {
+                                                                const float* __restrict__ temperature, float scale, float* __restrict__ dt_part,
+                                                                int n, int h) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ float dt_wave[LSA_WAVES];
   constexpr int DHP = DH < 32 ? 32 : DH, KP = DHP + 8, KS = DHP / 32, TP = LSA_NC + 8, NTC = LSA_NC / 16, ND = DH / 16;
@@ -456,7 +458,7 @@ __global__ __launch_bounds__(256) void attn_lsa_bwd_mfma_kernel(const bf16_t* __
       if (lr == 0 && r0 + 4 * lg + r < n) dsum_h[r0 + 4 * lg + r] = v;
     }
   }
-  const float et = expf(temperature[0]);
+  const float et = PLAIN ? scale : expf(temperature[0]);
   float dt_acc = 0.f;
   f32x4 acc1[ND], acc2[ND];
 #pragma unroll
@@ -486,11 +488,11 @@ __global__ __launch_bounds__(256) void attn_lsa_bwd_mfma_kernel(const bf16_t* __
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = r0 + 4 * lg + r;
-        const bool live = row < n && c < n && row != c;
+        const bool live = row < n && c < n && (PLAIN || row != c);
         const float sc = sa[r] * et;
         const float p = live ? expf(sc - (KEYS ? lc : lrow[r])) : 0.f;
         const float ds = p * (sb[r] - (KEYS ? Dc : Drow[r]));
-        if (!KEYS && live) dt_acc = fmaf(ds, sc, dt_acc);
+        if (!KEYS && !PLAIN && live) dt_acc = fmaf(ds, sc, dt_acc);
         Dt[(4 * lg + r) * TP + t * 16 + lr] = (bf16_t)(ds * et);
         if (KEYS) Pt[(4 * lg + r) * TP + t * 16 + lr] = (bf16_t)p;
       }
@@ -524,7 +526,7 @@ __global__ __launch_bounds__(256) void attn_lsa_bwd_mfma_kernel(const bf16_t* __
       }
     }
   }
-  if (!KEYS) {
+  if (!KEYS && !PLAIN) {
     dt_acc = wave_sum(dt_acc);
     if (lane == 0) dt_wave[wave] = dt_acc;
     __syncthreads();
@@ -532,20 +534,20 @@ __global__ __launch_bounds__(256) void attn_lsa_bwd_mfma_kernel(const bf16_t* __
       dt_part[((int64_t)bi * h + hi) * gridDim.x + blockIdx.x] = ((dt_wave[0] + dt_wave[1]) + dt_wave[2]) + dt_wave[3];
   }
 }
-template <int DH, bool KEYS>
+template <int DH, bool KEYS, bool PLAIN>
 void lsa_bwd_mfma_launch(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o, const float* lse, float* dsum, bf16_t* dqkv, int b, int n, int h,
-                         const float* t, float* part, hipStream_t s) {
+                         const float* t, float scale, float* part, hipStream_t s) {
   constexpr int DHP = DH < 32 ? 32 : DH, KP = DHP + 8, TP = LSA_NC + 8;
   const size_t lds = ((size_t)2 * LSA_NC * KP + (size_t)(KEYS ? 2 : 1) * DH * TP + (size_t)LSA_WAVES * (KEYS ? 2 : 1) * 16 * TP) * 2;
-  auto kern = attn_lsa_bwd_mfma_kernel<DH, KEYS>;
+  auto kern = attn_lsa_bwd_mfma_kernel<DH, KEYS, PLAIN>;
   vitx_set_max_smem((const void*)kern, LSA_LDS_MAX);
-  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, d_o, lse, dsum, dqkv, t, part, n, h);
+  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, d_o, lse, dsum, dqkv, t, scale, part, n, h);
 }
-template <int DH>
+template <int DH, bool PLAIN>
 void lsa_bwd_mfma_dh(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o, const float* lse, float* dsum, bf16_t* dqkv, int b, int n, int h,
-                     const float* t, float* part, hipStream_t s) {
-  lsa_bwd_mfma_launch<DH, false>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, part, s);   // (first: it writes the row sums the key pass reads)
-  lsa_bwd_mfma_launch<DH, true>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, part, s);
+                     const float* t, float scale, float* part, hipStream_t s) {
+  lsa_bwd_mfma_launch<DH, false, PLAIN>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);   // (first: it writes the row sums the key pass reads)
+  lsa_bwd_mfma_launch<DH, true, PLAIN>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
 }
 
 // second pass of the temperature gradient: one workgroup, every thread a fixed strided share, then a fixed tree
@@ -569,53 +571,53 @@ template <typename T, int DH> size_t lsa_bwd_lds(int n, int R, bool keys) {
   return (((size_t)2 * n * lsa_pitch<T, DH>() * sizeof(T) + 15) & ~(size_t)15) + (size_t)LSA_WAVES * (2 * R * DH + (keys ? 2 : 1) * R * lsa_npad(n)) * 4;
 }
 
-template <typename T, int DH, int R>
-void lsa_fwd_launch(const T* qkv, T* o, float* lse, int b, int n, int h, const float* t, size_t lds, hipStream_t s) {
-  auto kern = attn_lsa_fwd_kernel<T, DH, R>;
+template <typename T, int DH, int R, bool PLAIN>
+void lsa_fwd_launch(const T* qkv, T* o, float* lse, int b, int n, int h, const float* t, float scale, size_t lds, hipStream_t s) {
+  auto kern = attn_lsa_fwd_kernel<T, DH, R, PLAIN>;
   vitx_set_max_smem((const void*)kern, LSA_LDS_MAX);
-  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, lse, t, n, h);
+  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, lse, t, scale, n, h);
 }
-template <typename T, int DH>
-void lsa_fwd_dh(const T* qkv, T* o, float* lse, int b, int n, int h, const float* t, hipStream_t s) {
-  if (lsa_fwd_lds<T, DH>(n, 4) <= (size_t)LSA_LDS_MAX) lsa_fwd_launch<T, DH, 4>(qkv, o, lse, b, n, h, t, lsa_fwd_lds<T, DH>(n, 4), s);
-  else if (lsa_fwd_lds<T, DH>(n, 2) <= (size_t)LSA_LDS_MAX) lsa_fwd_launch<T, DH, 2>(qkv, o, lse, b, n, h, t, lsa_fwd_lds<T, DH>(n, 2), s);
-  else lsa_fwd_launch<T, DH, 1>(qkv, o, lse, b, n, h, t, lsa_fwd_lds<T, DH>(n, 1), s);
+template <typename T, int DH, bool PLAIN>
+void lsa_fwd_dh(const T* qkv, T* o, float* lse, int b, int n, int h, const float* t, float scale, hipStream_t s) {
+  if (lsa_fwd_lds<T, DH>(n, 4) <= (size_t)LSA_LDS_MAX) lsa_fwd_launch<T, DH, 4, PLAIN>(qkv, o, lse, b, n, h, t, scale, lsa_fwd_lds<T, DH>(n, 4), s);
+  else if (lsa_fwd_lds<T, DH>(n, 2) <= (size_t)LSA_LDS_MAX) lsa_fwd_launch<T, DH, 2, PLAIN>(qkv, o, lse, b, n, h, t, scale, lsa_fwd_lds<T, DH>(n, 2), s);
+  else lsa_fwd_launch<T, DH, 1, PLAIN>(qkv, o, lse, b, n, h, t, scale, lsa_fwd_lds<T, DH>(n, 1), s);
 }
 template <typename T>
 void lsa_fwd_t(const T* qkv, T* o, float* lse, int b, int n, int h, int dh, const float* t, hipStream_t s) {
-  if (dh == 64) lsa_fwd_dh<T, 64>(qkv, o, lse, b, n, h, t, s);
-  else if (dh == 32) lsa_fwd_dh<T, 32>(qkv, o, lse, b, n, h, t, s);
-  else lsa_fwd_dh<T, 16>(qkv, o, lse, b, n, h, t, s);
+  if (dh == 64) lsa_fwd_dh<T, 64, false>(qkv, o, lse, b, n, h, t, 0.f, s);
+  else if (dh == 32) lsa_fwd_dh<T, 32, false>(qkv, o, lse, b, n, h, t, 0.f, s);
+  else lsa_fwd_dh<T, 16, false>(qkv, o, lse, b, n, h, t, 0.f, s);
 }
 
-template <typename T, int DH, int R, bool KEYS>
-void lsa_bwd_launch(const T* qkv, const T* o, const T* d_o, const float* lse, float* dsum, T* dqkv, int b, int n, int h, const float* t, float* part,
-                    hipStream_t s) {
-  auto kern = attn_lsa_bwd_kernel<T, DH, R, KEYS>;
+template <typename T, int DH, int R, bool KEYS, bool PLAIN>
+void lsa_bwd_launch(const T* qkv, const T* o, const T* d_o, const float* lse, float* dsum, T* dqkv, int b, int n, int h, const float* t, float scale,
+                    float* part, hipStream_t s) {
+  auto kern = attn_lsa_bwd_kernel<T, DH, R, KEYS, PLAIN>;
   vitx_set_max_smem((const void*)kern, LSA_LDS_MAX);
   const size_t lds = lsa_bwd_lds<T, DH>(n, R, KEYS);
-  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, d_o, lse, dsum, dqkv, t, part, n, h);
+  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, d_o, lse, dsum, dqkv, t, scale, part, n, h);
 }
 // each pass with the most rows per wave whose LDS rows still fit beside the staged operands
-template <typename T, int DH, bool KEYS>
-void lsa_bwd_pass(const T* qkv, const T* o, const T* d_o, const float* lse, float* dsum, T* dqkv, int b, int n, int h, const float* t, float* part,
-                  hipStream_t s) {
-  if (lsa_bwd_lds<T, DH>(n, 4, KEYS) <= (size_t)LSA_LDS_MAX) lsa_bwd_launch<T, DH, 4, KEYS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, part, s);
-  else if (lsa_bwd_lds<T, DH>(n, 2, KEYS) <= (size_t)LSA_LDS_MAX) lsa_bwd_launch<T, DH, 2, KEYS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, part, s);
-  else lsa_bwd_launch<T, DH, 1, KEYS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, part, s);
+template <typename T, int DH, bool KEYS, bool PLAIN>
+void lsa_bwd_pass(const T* qkv, const T* o, const T* d_o, const float* lse, float* dsum, T* dqkv, int b, int n, int h, const float* t, float scale,
+                  float* part, hipStream_t s) {
+  if (lsa_bwd_lds<T, DH>(n, 4, KEYS) <= (size_t)LSA_LDS_MAX) lsa_bwd_launch<T, DH, 4, KEYS, PLAIN>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
+  else if (lsa_bwd_lds<T, DH>(n, 2, KEYS) <= (size_t)LSA_LDS_MAX) lsa_bwd_launch<T, DH, 2, KEYS, PLAIN>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
+  else lsa_bwd_launch<T, DH, 1, KEYS, PLAIN>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
 }
-template <typename T, int DH>
-void lsa_bwd_dh(const T* qkv, const T* o, const T* d_o, const float* lse, float* dsum, T* dqkv, int b, int n, int h, const float* t, float* part,
-                hipStream_t s) {
-  lsa_bwd_pass<T, DH, false>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, part, s);   // (first: it writes the row sums the key pass reads)
-  lsa_bwd_pass<T, DH, true>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, part, s);
+template <typename T, int DH, bool PLAIN>
+void lsa_bwd_dh(const T* qkv, const T* o, const T* d_o, const float* lse, float* dsum, T* dqkv, int b, int n, int h, const float* t, float scale,
+                float* part, hipStream_t s) {
+  lsa_bwd_pass<T, DH, false, PLAIN>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);   // (first: it writes the row sums the key pass reads)
+  lsa_bwd_pass<T, DH, true, PLAIN>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
 }
 template <typename T>
 void lsa_bwd_t(const T* qkv, const T* o, const T* d_o, const float* lse, float* dsum, T* dqkv, int b, int n, int h, int dh, const float* t, float* part,
                hipStream_t s) {
-  if (dh == 64) lsa_bwd_dh<T, 64>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, part, s);
-  else if (dh == 32) lsa_bwd_dh<T, 32>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, part, s);
-  else lsa_bwd_dh<T, 16>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, part, s);
+  if (dh == 64) lsa_bwd_dh<T, 64, false>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, 0.f, part, s);
+  else if (dh == 32) lsa_bwd_dh<T, 32, false>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, 0.f, part, s);
+  else lsa_bwd_dh<T, 16, false>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, 0.f, part, s);
 }
 
 }  // namespace
@@ -627,9 +629,9 @@ int64_t attn_lsa_ws_elems(int b, int n, int h) { return (int64_t)b * h * ceil_di
 
 void launch_attn_lsa_fwd(const void* qkv, void* o, float* lse, int is_bf16, int b, int n, int h, int dim_head, const float* temperature, hipStream_t s) {
   if (is_bf16) {
-    if (dim_head == 64) lsa_fwd_mfma_launch<64>((const bf16_t*)qkv, (bf16_t*)o, lse, b, n, h, temperature, s);
-    else if (dim_head == 32) lsa_fwd_mfma_launch<32>((const bf16_t*)qkv, (bf16_t*)o, lse, b, n, h, temperature, s);
-    else lsa_fwd_mfma_launch<16>((const bf16_t*)qkv, (bf16_t*)o, lse, b, n, h, temperature, s);
+    if (dim_head == 64) lsa_fwd_mfma_launch<64, false>((const bf16_t*)qkv, (bf16_t*)o, lse, b, n, h, temperature, 0.f, s);
+    else if (dim_head == 32) lsa_fwd_mfma_launch<32, false>((const bf16_t*)qkv, (bf16_t*)o, lse, b, n, h, temperature, 0.f, s);
+    else lsa_fwd_mfma_launch<16, false>((const bf16_t*)qkv, (bf16_t*)o, lse, b, n, h, temperature, 0.f, s);
   } else lsa_fwd_t<float>((const float*)qkv, (float*)o, lse, b, n, h, dim_head, temperature, s);
 }
 
@@ -637,9 +639,33 @@ void launch_attn_lsa_bwd(const void* qkv, const void* o, const void* d_o, const 
                          int dim_head, const float* temperature, float* dtemperature, float* part_ws, hipStream_t s) {
   if (is_bf16) {
     const bf16_t *q_ = (const bf16_t*)qkv, *o_ = (const bf16_t*)o, *do_ = (const bf16_t*)d_o;
-    if (dim_head == 64) lsa_bwd_mfma_dh<64>(q_, o_, do_, lse, dsum_ws, (bf16_t*)dqkv, b, n, h, temperature, part_ws, s);
-    else if (dim_head == 32) lsa_bwd_mfma_dh<32>(q_, o_, do_, lse, dsum_ws, (bf16_t*)dqkv, b, n, h, temperature, part_ws, s);
-    else lsa_bwd_mfma_dh<16>(q_, o_, do_, lse, dsum_ws, (bf16_t*)dqkv, b, n, h, temperature, part_ws, s);
+    if (dim_head == 64) lsa_bwd_mfma_dh<64, false>(q_, o_, do_, lse, dsum_ws, (bf16_t*)dqkv, b, n, h, temperature, 0.f, part_ws, s);
+    else if (dim_head == 32) lsa_bwd_mfma_dh<32, false>(q_, o_, do_, lse, dsum_ws, (bf16_t*)dqkv, b, n, h, temperature, 0.f, part_ws, s);
+    else lsa_bwd_mfma_dh<16, false>(q_, o_, do_, lse, dsum_ws, (bf16_t*)dqkv, b, n, h, temperature, 0.f, part_ws, s);
   } else lsa_bwd_t<float>((const float*)qkv, (const float*)o, (const float*)d_o, lse, dsum_ws, (float*)dqkv, b, n, h, dim_head, temperature, part_ws, s);
   hipLaunchKernelGGL(attn_lsa_dtemp_kernel, dim3(1), dim3(256), 0, s, part_ws, attn_lsa_ws_elems(b, n, h), dtemperature);
+}
+
+// Plain small-head attention (nest.py:93-109, on a vitx_config.nest_block engine): the kernels above in their PLAIN mode -- no diagonal mask, the scale
+// dim_head^-0.5 passed by value, no temperature partials and no second pass, n >= 1.  dim_head 64 keeps attn_bf16 / attn_x3.
+bool attn_small_supported(int n, int dim_head) { return (dim_head == 16 || dim_head == 32) && n >= 1 && n <= LSA_N_MAX; }
+
+void launch_attn_small_fwd(const void* qkv, void* o, float* lse, int is_bf16, int b, int n, int h, int dim_head, float scale, hipStream_t s) {
+  if (is_bf16) {
+    if (dim_head == 32) lsa_fwd_mfma_launch<32, true>((const bf16_t*)qkv, (bf16_t*)o, lse, b, n, h, nullptr, scale, s);
+    else lsa_fwd_mfma_launch<16, true>((const bf16_t*)qkv, (bf16_t*)o, lse, b, n, h, nullptr, scale, s);
+  } else if (dim_head == 32) lsa_fwd_dh<float, 32, true>((const float*)qkv, (float*)o, lse, b, n, h, nullptr, scale, s);
+  else lsa_fwd_dh<float, 16, true>((const float*)qkv, (float*)o, lse, b, n, h, nullptr, scale, s);
+}
+
+void launch_attn_small_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, float* dsum_ws, void* dqkv, int is_bf16, int b, int n, int h,
+                           int dim_head, float scale, hipStream_t s) {
+  if (is_bf16) {
+    const bf16_t *q_ = (const bf16_t*)qkv, *o_ = (const bf16_t*)o, *do_ = (const bf16_t*)d_o;
+    if (dim_head == 32) lsa_bwd_mfma_dh<32, true>(q_, o_, do_, lse, dsum_ws, (bf16_t*)dqkv, b, n, h, nullptr, scale, nullptr, s);
+    else lsa_bwd_mfma_dh<16, true>(q_, o_, do_, lse, dsum_ws, (bf16_t*)dqkv, b, n, h, nullptr, scale, nullptr, s);
+  } else if (dim_head == 32)
+    lsa_bwd_dh<float, 32, true>((const float*)qkv, (const float*)o, (const float*)d_o, lse, dsum_ws, (float*)dqkv, b, n, h, nullptr, scale, nullptr, s);
+  else
+    lsa_bwd_dh<float, 16, true>((const float*)qkv, (const float*)o, (const float*)d_o, lse, dsum_ws, (float*)dqkv, b, n, h, nullptr, scale, nullptr, s);
 }

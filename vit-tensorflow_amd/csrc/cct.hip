@@ -11,6 +11,7 @@
 #include <cstring>
 
 #include "composite.h"
+#include "conv_same.h"
 
 namespace {
 
@@ -119,57 +120,6 @@ __global__ void cct_add_pos_kernel(const float* __restrict__ x, const float* __r
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < total) out[e] = x[e] + pos[e % per_image];
 }
-// dst = first ? src : dst + src   (weight-gradient partials of the image chunks, summed in chunk order)
-__global__ void cct_accum_kernel(float* __restrict__ dst, const float* __restrict__ src, int64_t n, int first) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) dst[e] = first ? src[e] : dst[e] + src[e];
-}
-
-// a launch (or a group of launches) booked under a kernel class of the engine's profiler (vitx_cct_profile_begin / _end)
-struct CctProf {
-  vitx_engine* e;
-  ProfEvent pe{};
-  bool on;
-  CctProf(vitx_engine* e_, const char* name) : e(e_), on(e_->profiling) {
-    if (!on) return;
-    pe.cls = prof_class(e, name);
-    pe.cls2 = -1; pe.flops = 0; pe.bytes = 0;
-    (void)hipEventCreate(&pe.e0);
-    (void)hipEventCreate(&pe.e1);
-    (void)hipEventRecord(pe.e0, e->stream);
-  }
-  ~CctProf() {
-    if (!on) return;
-    (void)hipEventRecord(pe.e1, e->stream);
-    e->prof_events.push_back(pe);
-  }
-};
-
-// Weight gradient of a convolution: dWp[Kp, N] = rows[M, Kp]^T dY[M, N] over all Kp (>= 64) padded columns.  On the split-operand kernel the M token
-// rows are cut into slices (the kernel's batch index, the last one shorter) so that tiles x slices fills the chip; the fp32 partials are summed in
-// slice order by launch_reduce_partials.  `part` holds max_slices * Kp * N floats.  The first K * N floats of dWp are the kernel's gradient.
-constexpr int CONV_WGRAD_SLICES = 32;
-void conv_wgrad(const float* rows, int Kp, const float* dY, float* dWp, float* part, int M, int N, int x3, hipStream_t s) {
-  GenericGemmArgs g;
-  g.A = rows; g.B = dY; g.M = Kp; g.N = N; g.K = M; g.sam = 1; g.sak = Kp; g.sbk = N; g.sbn = 1; g.x3 = x3;
-  EpiParams ep;
-  ep.out = dWp; ep.ldo = N; ep.M = Kp; ep.N = N; ep.vec_ok = (N % 4 == 0) && aligned16({dWp, part});
-  int slices = 1;
-  if (x3 && gemm_bf16x3_supported(g, 0, 0, 0)) {
-    const int64_t tiles = ceil_div(Kp, 128) * ceil_div(N, 128);
-    const int64_t want = std::min<int64_t>({std::max<int64_t>(1, 1024 / tiles), std::max<int64_t>(1, M / 256), CONV_WGRAD_SLICES});
-    if (want > 1) {
-      const int ks = (int)round_up(ceil_div(M, want), 32);
-      slices = (int)ceil_div(M, ks);
-      if (slices > 1) {
-        g.K = ks; g.nb = slices; g.sAb = (int64_t)ks * Kp; g.sBb = (int64_t)ks * N; g.k_last = M - (slices - 1) * ks;
-        ep.out = part; ep.out_batch_stride = (int64_t)Kp * N;
-      }
-    }
-  }
-  launch_gemm_generic(g, ep, EPI_STORE_F32, 0, 0, 0, s);
-  if (slices > 1) launch_reduce_partials(part, slices, (int64_t)Kp * N, (int64_t)Kp * N, dWp, 1.0f, s);
-}
 // one conv layer of the tokenizer and the geometry of its two 'SAME' stages
 struct ConvLayer {
   int H = 0, W = 0, Cin = 0, Cout = 0;   // input extent / planes, filters
@@ -181,7 +131,6 @@ struct ConvLayer {
   float *conv = nullptr, *pooled = nullptr;   // [B, oh, ow, Cout] pre-activation (kept for the VJP), [B, ph, pw, Cout]
 };
 
-constexpr int64_t IM2COL_BUDGET = 32ll << 20;   // floats of one im2col chunk (128 MB); a single image may exceed it
 
 }  // namespace
 
@@ -414,11 +363,11 @@ int cct_forward(vitx_cct* m, const float* img_dev, int b, std::string& err) {
     const int64_t in_img = (int64_t)L.H * L.W * L.Cin, out_img = (int64_t)L.oh * L.ow * L.Cout;
     for (int b0 = 0; b0 < b; b0 += L.chunk) {
       const int nb = std::min(L.chunk, b - b0);
-      { CctProf pr(m->eng, "cct_im2col"); launch_cct_im2col(x + b0 * in_img, m->rows, nb, L.H, L.W, L.Cin, c.kernel_size, c.stride, L.Kp, s); }
-      CctProf pr(m->eng, "cct_conv_gemm");
+      { CompositeProf pr(m->eng, "cct_im2col"); launch_cct_im2col(x + b0 * in_img, m->rows, nb, L.H, L.W, L.Cin, c.kernel_size, c.stride, L.Kp, s); }
+      CompositeProf pr(m->eng, "cct_conv_gemm");
       dense_fwd(m->rows, L.Kp, P + L.w, nullptr, L.conv + b0 * out_img, nb * L.oh * L.ow, L.Cout, L.K, s, m->x3);
     }
-    CctProf pr(m->eng, "cct_relu_maxpool_fwd");
+    CompositeProf pr(m->eng, "cct_relu_maxpool_fwd");
     launch_cct_relu_maxpool_fwd(L.conv, L.pooled, b, L.oh, L.ow, L.Cout, c.pooling_kernel_size, c.pooling_stride, s);
     x = L.pooled;
   }
@@ -434,7 +383,7 @@ int cct_forward(vitx_cct* m, const float* img_dev, int b, std::string& err) {
   if ((rc = engine_transformer_forward(m->eng, tok, b, n, 0, 0, m->enc, err)) != VITX_OK) return rc;                               // :290
   launch_layernorm_fwd(m->enc, d, P + m->norm_g, P + m->norm_b, m->xn, 0, d, m->mean, m->rstd, b * n, d, c.ln_eps, s);               // :291
   {
-    CctProf pr(m->eng, "cct_seqpool_fwd");
+    CompositeProf pr(m->eng, "cct_seqpool_fwd");
     hipLaunchKernelGGL(cct_seqpool_fwd_kernel, dim3((unsigned)b), dim3(SP_THREADS), seqpool_lds_bytes(n, false), s, m->xn, P + m->pool_w, P + m->pool_b,
                        m->p, m->pooled, n, d);                                                                                       // :293-299
   }
@@ -459,7 +408,7 @@ int cct_backward(vitx_cct* m, const float* dlogits_dev, float* dimg_dev, std::st
   dense_dx(dlogits_dev, P + m->fc_w, m->dpooled, b, m->nc, d, s);
   // sequence pooling: per-image partials, then a fixed-order sum over the images
   {
-    CctProf pr(m->eng, "cct_seqpool_bwd");
+    CompositeProf pr(m->eng, "cct_seqpool_bwd");
     hipLaunchKernelGGL(cct_seqpool_bwd_kernel, dim3((unsigned)b), dim3(SP_THREADS), seqpool_lds_bytes(n, true), s, m->xn, P + m->pool_w, m->p, m->dpooled,
                        m->dxn, m->dwp, m->dbp, n, d);
     launch_sum_rows(m->dwp, b, d, G + m->pool_w, s);
@@ -481,23 +430,23 @@ int cct_backward(vitx_cct* m, const float* dlogits_dev, float* dimg_dev, std::st
     const float* xin = i == 0 ? (const float*)m->img : m->conv[(size_t)i - 1].pooled;
     float* dxin = i == 0 ? dimg_dev : m->dact[i & 1];
     {
-      CctProf pr(m->eng, "cct_relu_maxpool_bwd");
+      CompositeProf pr(m->eng, "cct_relu_maxpool_bwd");
       launch_cct_relu_maxpool_bwd(L.conv, dpool, m->dconv, b, L.oh, L.ow, L.Cout, c.pooling_kernel_size, c.pooling_stride, s);
     }
     for (int b0 = 0; b0 < b; b0 += L.chunk) {
       const int nb = std::min(L.chunk, b - b0);
       const int rows = nb * L.oh * L.ow;
       const float* dy = m->dconv + b0 * out_img;
-      { CctProf pr(m->eng, "cct_im2col"); launch_cct_im2col(xin + b0 * in_img, m->rows, nb, L.H, L.W, L.Cin, c.kernel_size, c.stride, L.Kp, s); }
+      { CompositeProf pr(m->eng, "cct_im2col"); launch_cct_im2col(xin + b0 * in_img, m->rows, nb, L.H, L.W, L.Cin, c.kernel_size, c.stride, L.Kp, s); }
       {
-        CctProf pr(m->eng, "cct_conv_gemm");
+        CompositeProf pr(m->eng, "cct_conv_gemm");
         conv_wgrad(m->rows, L.Kp, dy, m->gw_part, m->gw_slices, rows, L.Cout, m->x3, s);
         const int64_t nw = (int64_t)L.K * L.Cout;
-        hipLaunchKernelGGL(cct_accum_kernel, dim3(grid256(nw)), dim3(256), 0, s, G + L.w, (const float*)m->gw_part, nw, b0 == 0 ? 1 : 0);
+        hipLaunchKernelGGL(conv_accum_kernel, dim3(grid256(nw)), dim3(256), 0, s, G + L.w, (const float*)m->gw_part, nw, b0 == 0 ? 1 : 0);
         if (dxin) dense_dx(dy, P + L.w, m->drows, rows, L.Cout, L.K, s, m->x3);
       }
       if (dxin) {
-        CctProf pr(m->eng, "cct_col2im");
+        CompositeProf pr(m->eng, "cct_col2im");
         launch_extract_patches_bwd(m->drows, dxin + b0 * in_img, nb, L.H, L.W, L.Cin, c.kernel_size, c.stride, s);
       }
     }

@@ -220,6 +220,7 @@ struct vitx_engine {
   int64_t sc_keep_bytes = 0, sc_keep_budget = 48LL << 30;
   // env switches
   bool force_generic_gemm = false, force_generic_attn = false, wgrad_via_transpose = true;
+  bool small_attn = true;   // nest_block handles: plain small-head attention kernels where they apply; nest.hip sets it per handle (vitx_nest_config.small_attn)
   int gemm_kernel = 0;
   int gemm_tail = 0;      // forced tail variant (VITX_GEMM_TAIL_KERNEL; only with a forced main variant)
   int reverse_mask = 7;                  // VITX_REVERSE=bits: 1 forward GEMMs, 2 dgrad GEMMs walk their row tiles last-to-first when the A operand exceeds

@@ -40,6 +40,11 @@ std::string build_param_table(const vitx_config& c, std::vector<ParamDesc>& out)
   if (cctb && c.num_parallel_branches > 1) return "cct_block does not combine with num_parallel_branches";
   if (cctb && sd) return "cct_block does not combine with small_dataset";
   if (cctb && c.dropout != 0.f) return "cct_block needs dropout == 0 (CCT hard-wires dropout_rate=0, cct.py:336)";
+  const bool nestb = c.nest_block != 0;   // nest.py:77-148
+  if (nestb && c.variant != VITX_VARIANT_VIT) return "nest_block needs the ViT variant";
+  if (nestb && c.num_parallel_branches > 1) return "nest_block does not combine with num_parallel_branches";
+  if (nestb && sd) return "nest_block does not combine with small_dataset";
+  if (nestb && cctb) return "nest_block does not combine with cct_block";
   const int64_t pd = (int64_t)c.patch_h * c.patch_w * c.channels * (sd ? 5 : 1);   // SPT: the image and its four shifts (vit_for_small_dataset.py:154)
   int64_t off = 0, aoff = 0;
   auto add = [&](const std::string& n, std::vector<int64_t> s) {
@@ -82,7 +87,7 @@ std::string build_param_table(const vitx_config& c, std::vector<ParamDesc>& out)
       add(pre + ".attn.reattn_norm.gamma", {h});
       add(pre + ".attn.reattn_norm.beta", {h});
     }
-    const bool project_out = sd || cctb || !((c.variant == VITX_VARIANT_VIT || merger) && h == 1 && dh == d);  // vit.py:53; LSA always projects (vit_for_small_dataset.py:99-102), so does CCT (cct.py:117-122)
+    const bool project_out = sd || cctb || nestb || !((c.variant == VITX_VARIANT_VIT || merger) && h == 1 && dh == d);  // vit.py:53; LSA always projects (vit_for_small_dataset.py:99-102), so do CCT (cct.py:117-122) and NesT (nest.py:88-91)
     if (project_out) {
       add(pre + ".attn.to_out.kernel", {inner, d});
       add(pre + ".attn.to_out.bias", {d});
@@ -993,6 +998,10 @@ static void attn_generic_bwd(vitx_engine* e, const BlockParams& bp, const AttnVi
              BgemmCall{dA, 0, 1, ld, bs, hs, a.q, T, a.ldq, 1, a.qb, dh, a.nk, dh, a.nq, b, h, EPI_STORE, T, gr.dk, gr.lddk, gr.dkb, dh, scale});
 }
 
+// nest_block handles: the plain-softmax form of the small-head kernels (attn_lsa.hip) where the fused kernels above do not apply
+static bool use_small_attn(const vitx_engine* e, int n) {
+  return e->cfg.nest_block && e->small_attn && !e->force_generic_attn && attn_small_supported(n, e->cfg.dim_head);
+}
 static bool use_fused_attn(const vitx_engine* e, int n) {
   return e->bf16 && e->cfg.variant == VITX_VARIANT_VIT && !e->force_generic_attn && attn_bf16_supported(n, e->cfg.dim_head);
 }
@@ -1053,6 +1062,9 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
   if (c.small_dataset) {   // LSA (vit_for_small_dataset.py:109-117): learned temperature, masked diagonal
     Prof pr(e, "attn_lsa_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
     launch_attn_lsa_fwd(ba.qkv, ba.o, ba.lse, T, b, nq, c.heads, c.dim_head, e->params + bp.temp, e->stream);
+  } else if (use_small_attn(e, nq)) {   // nest.py:101-105
+    Prof pr(e, "attn_small_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
+    launch_attn_small_fwd(ba.qkv, ba.o, ba.lse, T, b, nq, c.heads, c.dim_head, 1.0f / std::sqrt((float)c.dim_head), e->stream);
   } else if (use_fused_attn_x3(e, nq)) {
     Prof pr(e, "attn_x3_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
     launch_attn_x3_fwd((const float*)ba.qkv, (float*)ba.o, ba.lse, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), e->stream);
@@ -1369,6 +1381,9 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
       Prof pr(e, "attn_lsa_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
       launch_attn_lsa_bwd(ba.qkv, ba.o, d_o, ba.lse, e->dsum, e->d_qkv, T, b, nq, c.heads, c.dim_head, e->params + bp.temp, e->grads + bp.temp,
                           e->lsa_ws, e->stream);
+    } else if (use_small_attn(e, nq)) {
+      Prof pr(e, "attn_small_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
+      launch_attn_small_bwd(ba.qkv, ba.o, d_o, ba.lse, e->dsum, e->d_qkv, T, b, nq, c.heads, c.dim_head, 1.0f / std::sqrt((float)c.dim_head), e->stream);
     } else if (use_fused_attn_x3(e, nq)) {
       Prof pr(e, "attn_x3_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
       launch_attn_x3_bwd((const float*)ba.qkv, (const float*)ba.o, (const float*)d_o, ba.lse, (float*)e->d_qkv, b, nq, c.heads,
@@ -1977,6 +1992,7 @@ int engine_forward(vitx_engine* e, const float* img_dev, int b, int H, int W, in
   const float* patches_in = e->fwd_patches;
   e->fwd_patches = nullptr;
   if (c.cct_block) { err = "cct_block handles serve vitx_cct_* through the transformer entry points only"; return VITX_ERR_UNSUPPORTED; }
+  if (c.nest_block) { err = "nest_block handles serve vitx_nest_* through the transformer entry points only"; return VITX_ERR_UNSUPPORTED; }
   if (c.small_dataset && (patches_in || extra)) { err = "small_dataset handles take images only (no patch rows, no distillation token)"; return VITX_ERR_UNSUPPORTED; }
   if (patches_in) {
     if (e->fwd_np <= 0 || e->fwd_np > e->np_max) { err = "forward_patches: np must be in [1, num_patches]"; return VITX_ERR_INVALID; }
@@ -2080,6 +2096,7 @@ static int shell_check(const vitx_engine* e, std::string& err) {
   if (c.num_parallel_branches > 1) { err = "embed / head entry points: not for parallel_vit handles"; return VITX_ERR_UNSUPPORTED; }
   if (c.small_dataset) { err = "embed / head entry points: not for small_dataset handles"; return VITX_ERR_UNSUPPORTED; }
   if (c.cct_block) { err = "embed / head entry points: not for cct_block handles"; return VITX_ERR_UNSUPPORTED; }
+  if (c.nest_block) { err = "embed / head entry points: not for nest_block handles"; return VITX_ERR_UNSUPPORTED; }
   return VITX_OK;
 }
 
@@ -2299,6 +2316,7 @@ int engine_patch_tokens_forward(vitx_engine* e, const float* img_dev, int b, int
   if (c.variant == VITX_VARIANT_CAIT || c.variant == VITX_VARIANT_PATCH_MERGER) { err = "patch_tokens_forward: ViT / DeepViT only"; return VITX_ERR_UNSUPPORTED; }
   if (c.small_dataset) { err = "patch_tokens_forward: not for small_dataset handles"; return VITX_ERR_UNSUPPORTED; }
   if (c.cct_block) { err = "patch_tokens_forward: not for cct_block handles"; return VITX_ERR_UNSUPPORTED; }
+  if (c.nest_block) { err = "patch_tokens_forward: not for nest_block handles"; return VITX_ERR_UNSUPPORTED; }
   if (b <= 0 || b > c.max_batch) { err = "batch must be in [1, max_batch]"; return VITX_ERR_INVALID; }
   if (H <= 0 || W <= 0 || H > c.image_h || W > c.image_w || H % c.patch_h || W % c.patch_w) {
     err = "Image dimensions must be divisible by the patch size.";

@@ -99,6 +99,12 @@ void launch_attn_lsa_fwd(const void* qkv, void* o, float* lse, int is_bf16, int 
 // dsum_ws: b * h * n floats; *dtemperature is overwritten (fixed-order two-pass sum)
 void launch_attn_lsa_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, float* dsum_ws, void* dqkv, int is_bf16, int b, int n, int h,
                          int dim_head, const float* temperature, float* dtemperature, float* part_ws, hipStream_t s);
+// plain small-head attention (nest.py:93-109): the same kernels compiled without the diagonal mask and the temperature, softmax scale by value;
+// dim_head in {16, 32}, 1 <= n <= LSA_N_MAX
+bool attn_small_supported(int n, int dim_head);
+void launch_attn_small_fwd(const void* qkv, void* o, float* lse, int is_bf16, int b, int n, int h, int dim_head, float scale, hipStream_t s);
+void launch_attn_small_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, float* dsum_ws, void* dqkv, int is_bf16, int b, int n, int h,
+                           int dim_head, float scale, hipStream_t s);
 
 // ---------------------------------------------------------------- spt.hip
 // shifted patch tokenization (vit_for_small_dataset.py:15-47,142-157): NHWC image -> LayerNorm'ed rows [b * np, 5 p p C] of the image concatenated
@@ -120,6 +126,19 @@ void launch_cct_im2col(const float* x, float* rows, int b, int H, int W, int C, 
 void launch_cct_relu_maxpool_fwd(const float* conv, float* out, int b, int H, int W, int C, int k, int st, hipStream_t s);
 // its VJP in gather form (every element of dconv written; first maximum in row-major window order takes a window; no atomics)
 void launch_cct_relu_maxpool_bwd(const float* conv, const float* dout, float* dconv, int b, int H, int W, int C, int k, int st, hipStream_t s);
+
+// ---------------------------------------------------------------- nest_ops.hip
+// NesT (nest.py:137-148,207-212): block partition fused with the positional add, its inverse, their VJPs, and the plain 'SAME' max-pool
+// tokens[(b b1 b2), (h w), c] = x[b, (b1 h), (b2 w), c] + pos[h * w_ + w]   (x: [b, nb * hb, nb * wb, c]; pos == nullptr: the pure copy)
+void launch_nest_to_blocks(const float* x, const float* pos, float* tokens, int b, int nb, int hb, int wb, int c, hipStream_t s);
+// x[b, (b1 h), (b2 w), c] = tokens[(b b1 b2), (h w), c]
+void launch_nest_from_blocks(const float* tokens, float* x, int b, int nb, int hb, int wb, int c, hipStream_t s);
+// d(pos)[j] = sum over sequences and channels of dtokens[seq, j, :]: one partial row per sequence (part: [nseq, n]), then launch_sum_rows
+void launch_nest_dpos(const float* dtokens, float* part, float* dpos, int nseq, int n, int c, hipStream_t s);
+// MaxPool2D(padding='SAME') on a signed input (the running maximum starts at -inf; taps outside the map never win) and its gather-form VJP
+// (every element of dx written; the first maximum in row-major window order takes the window's gradient; no atomics)
+void launch_nest_maxpool_fwd(const float* x, float* out, int b, int H, int W, int C, int k, int st, hipStream_t s);
+void launch_nest_maxpool_bwd(const float* x, const float* dout, float* dx, int b, int H, int W, int C, int k, int st, hipStream_t s);
 
 // ---------------------------------------------------------------- elementwise.hip
 void launch_unfold(const float* img, void* out, int out_bf16, int b, int H, int W, int C, int ph, int pw,

@@ -23,10 +23,16 @@ class VitxError(RuntimeError):
         self.message = msg
 
 
+class _ConfigFlags(C.Structure):
+    _fields_ = [("cct_block", C.c_int32), ("nest_block", C.c_int32)]
+
+
 class _ConfigTail(C.Union):
-    """The last four words of vitx_config.  include/vitx.h carved cct_block out of the first reserved word; `reserved` keeps its four-word view
-    here (reserved[0] is cct_block), so code that zeroes or inspects it by that name sees the layout it always saw."""
-    _fields_ = [("reserved", C.c_int32 * 4), ("cct_block", C.c_int32)]
+    """The last four words of vitx_config.  include/vitx.h carved cct_block and nest_block out of the first two reserved words; `reserved` keeps
+    its four-word view here (reserved[0] is cct_block, reserved[1] nest_block), so code that zeroes or inspects it by that name sees the layout
+    it always saw."""
+    _anonymous_ = ("_flags",)
+    _fields_ = [("reserved", C.c_int32 * 4), ("_flags", _ConfigFlags)]
 
 
 class Config(C.Structure):
@@ -88,6 +94,15 @@ class CCTConfig(C.Structure):
 
 
 CCT_POS = {"learnable": 0, "sine": 1, "none": 2}
+
+
+class NesTConfig(C.Structure):
+    _fields_ = [
+        ("image_size", C.c_int32), ("patch_size", C.c_int32), ("num_classes", C.c_int32), ("dim", C.c_int32), ("heads", C.c_int32),
+        ("num_hierarchies", C.c_int32), ("block_repeats", C.c_int32 * 8), ("mlp_mult", C.c_int32),
+        ("ln_eps", C.c_float), ("compute", C.c_int32), ("max_batch", C.c_int32), ("device_id", C.c_int32), ("conv_chunk", C.c_int32),
+        ("small_attn", C.c_int32), ("reserved", C.c_int32 * 7),
+    ]
 
 
 class CrossViTConfig(C.Structure):
@@ -239,6 +254,23 @@ SYMBOLS: List[Tuple[str, object, list]] = [
     ("vitx_cct_profile_begin", C.c_int32, [C.c_void_p]),
     ("vitx_cct_profile_end", C.c_int32, [C.c_void_p, _P(KernelStat), C.c_int32, _P(C.c_int32)]),
     ("vitx_cct_read", C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, _P(C.c_int64)]),
+    ("vitx_nest_param_table_size", C.c_int32, [_P(NesTConfig), _P(C.c_int64), _P(C.c_int64)]),
+    ("vitx_nest_param_table_entry", C.c_int32, [_P(NesTConfig), C.c_int64, C.c_char_p, C.c_int32, _P(C.c_int64), _P(C.c_int32), _P(C.c_int64)]),
+    ("vitx_nest_create", C.c_int32, [_P(NesTConfig), _P(C.c_void_p)]),
+    ("vitx_nest_destroy", C.c_int32, [C.c_void_p]),
+    ("vitx_nest_set_params", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_nest_get_params", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_nest_get_grads", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_nest_params_dev", C.c_int32, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)]),
+    ("vitx_nest_grads_dev", C.c_int32, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)]),
+    ("vitx_nest_params_changed", C.c_int32, [C.c_void_p]),
+    ("vitx_nest_forward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("vitx_nest_forward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("vitx_nest_backward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("vitx_nest_backward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("vitx_nest_profile_begin", C.c_int32, [C.c_void_p]),
+    ("vitx_nest_profile_end", C.c_int32, [C.c_void_p, _P(KernelStat), C.c_int32, _P(C.c_int32)]),
+    ("vitx_nest_read", C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, _P(C.c_int64)]),
 ]
 
 _lib = None
@@ -295,6 +327,11 @@ def crossvit_param_table(cfg: CrossViTConfig):
 def cct_param_table(cfg: CCTConfig):
     """[(name, shape, offset)] of CCT's variables from the C library (host-only call; no GPU needed)."""
     return table_of("vitx_cct", C.byref(cfg))
+
+
+def nest_param_table(cfg: NesTConfig):
+    """[(name, shape, offset)] of NesT's variables from the C library (host-only call; no GPU needed)."""
+    return table_of("vitx_nest", C.byref(cfg))
 
 
 def mim_param_table(handle, prefix="vitx_mim"):
