@@ -166,7 +166,10 @@ __device__ __forceinline__ void fwd_max_pair(const char* k_rm, int u, int qi, in
 
 template <int NTP>
 __global__ __launch_bounds__(ATT_THREADS, 4) void attn_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o, float* __restrict__ lse,
-                                                       int n, int h, float scale, const bf16_t* __restrict__ zero_page, int reverse, int planar) {
+                                                       int n, int h, float scale, const bf16_t* __restrict__ zero_page, int reverse, int planar,
+                                                       int nq_live) {
+  // nq_live (1 <= nq_live <= n): only the query blocks that hold a row < nq_live are computed, and only rows < nq_live of o / lse are stored (the last
+  // block under cls pooling: nothing reads the other rows).  Every key stays: the arithmetic of a computed row is that of the full launch.
   constexpr int NKP = 16 * NTP, QB = QB_FWD;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* k_rm = smem;                                   // [NKP][128 B] swizzled
@@ -182,7 +185,7 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attn_fwd_kernel(const bf16_t* 
   stage_head_dma(qbase + 2 * L.kv_off, tok_stride, n, NKP, v_rm, zero_page, wave, lane, nwaves);
 
   const int qi = lane & 15, g = lane >> 4;
-  const int nqb = (n + 16 * QB - 1) / (16 * QB);
+  const int nqb = (nq_live + 16 * QB - 1) / (16 * QB);
   const float sl2 = scale * 1.44269504088896340736f;
   bf16x8 qf[QB][2];
   auto load_q = [&](int qb) {                        // rows >= n of the last block compute on the clamped row n-1 and are never stored
@@ -236,8 +239,8 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attn_fwd_kernel(const bf16_t* 
       ls += __shfl_xor(ls, 16, 64);
       ls += __shfl_xor(ls, 32, 64);
       const float inv_l = 1.0f / ls;
-      if (g == 0 && q < n) lse[(int64_t)bh * n + q] = (m[s] + log2f(ls)) * 0.69314718055994530942f;  // natural-log LSE
-      if (q < n) {
+      if (g == 0 && q < nq_live) lse[(int64_t)bh * n + q] = (m[s] + log2f(ls)) * 0.69314718055994530942f;  // natural-log LSE
+      if (q < nq_live) {
         bf16_t* op = o + L.o0 + (int64_t)q * L.o_stride;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -314,7 +317,7 @@ __device__ __forceinline__ void dq_load(DqOperands& x, const bf16_t* qbase, int6
 
 template <int NTP>
 __device__ __forceinline__ float dq_block(const char* k_rm, const char* v_rm, const DqOperands& x, int64_t tok_stride, bf16_t* dq_rows, int qb, int lane,
-                                          int n, float scale, float lse2) {
+                                          int n, float scale, float lse2, int nq_live) {
   const int qi = lane & 15, g = lane >> 4;
   const int q = qb * 16 + qi;
   const float sl2 = scale * 1.44269504088896340736f;
@@ -335,7 +338,7 @@ __device__ __forceinline__ float dq_block(const char* k_rm, const char* v_rm, co
 #pragma unroll 1
   for (int u = 0; u < u_full; ++u) dq_pair<false>(k_rm, v_rm, u, qi, g, lane, n, qf, dof, sl2, lse2, scale, nds, dq);
   if (u_full < u_end) dq_pair<true>(k_rm, v_rm, u_full, qi, g, lane, n, qf, dof, sl2, lse2, scale, nds, dq);
-  if (q < n) {
+  if (q < nq_live) {
     bf16_t* out = dq_rows + (int64_t)q * tok_stride;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -344,13 +347,22 @@ __device__ __forceinline__ float dq_block(const char* k_rm, const char* v_rm, co
       for (int r = 0; r < 4; ++r) ov[r] = (bf16_t)dq[c][r];
       *(bf16x4*)(out + 16 * c + 4 * g) = ov;
     }
+  } else if (q < n) {   // a dead row of a live block (no LSE was stored for it): zero, as its dO = 0 makes it in the full launch
+    bf16_t* out = dq_rows + (int64_t)q * tok_stride;
+    bf16x4 z;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) z[r] = (bf16_t)0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) *(bf16x4*)(out + 16 * c + 4 * g) = z;
   }
   return dsum;
 }
 
 // One 16-key block of the dK / dV pass (Q, dO images in LDS; lse_s (log2 domain) and d_s per query in LDS, rows >= n: 0).
 // No masks: query rows >= n are zero rows of q / dO with lse = D = 0, so their P = 1 meets dO = 0 and their dS = 1 * (0 - 0); key lanes >= n
-// compute on the clamped key n-1 and are never stored.  Tile pairs past n are skipped.
+// compute on the clamped key n-1 and are never stored.  Tile pairs past n are skipped.  With a live-query count nq < n the same invariant covers
+// the dead queries: the caller stages rows >= nq of q / dO from the zero page with lse = D = 0, and the tile pairs past nq are skipped -- they would add
+// exact zeros (dO = 0), so dk / dv keep the bits of the full launch.
 struct DkvOperands { bf16x8 kf[2], vf[2]; };   // one 16-key block's k and v rows (the B operands of S and dP), loaded one block ahead as well
 __device__ __forceinline__ void dkv_load(DkvOperands& x, const bf16_t* kbase, int64_t tok_stride, int64_t inner, int kb, int lane, int n) {
   const int kc = min(kb * 16 + (lane & 15), n - 1), g = lane >> 4;
@@ -363,7 +375,7 @@ __device__ __forceinline__ void dkv_load(DkvOperands& x, const bf16_t* kbase, in
 
 template <int NTP>
 __device__ __forceinline__ void dkv_block(const char* q_rm, const char* do_rm, const float* lse_s, const float* d_s, const DkvOperands& x,
-                                          int64_t tok_stride, int64_t inner, bf16_t* dk_rows, int kb, int lane, int n, float scale) {
+                                          int64_t tok_stride, int64_t inner, bf16_t* dk_rows, int kb, int lane, int n, float scale, int nq) {
   const int ki = lane & 15, g = lane >> 4;
   const int key = kb * 16 + ki;
   const float sl2 = scale * 1.44269504088896340736f;
@@ -372,7 +384,7 @@ __device__ __forceinline__ void dkv_block(const char* q_rm, const char* do_rm, c
   f32x4 dk[4], dv[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) { dk[c] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[c] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-  const int u_end = min(NTP / 2, (n + 31) >> 5);
+  const int u_end = min(NTP / 2, (nq + 31) >> 5);
 #pragma unroll 1
   for (int u = 0; u < u_end; ++u) {
     f32x4 pp[2], ds[2];
@@ -418,12 +430,18 @@ __device__ __forceinline__ void dkv_block(const char* q_rm, const char* do_rm, c
   }
 }
 
+// dq rows of the query blocks a restricted dQ pass did not compute (blocks >= nblk_live): written as zeros, so that d(qkv) needs no fill
+__device__ __forceinline__ void dq_zero_dead_blocks(bf16_t* dq_rows, int64_t tok_stride, int nblk_live, int n, int tid, int nthreads) {
+  for (int idx = tid; idx < (n - 16 * nblk_live) * 8; idx += nthreads)
+    *(bf16x8*)(dq_rows + (int64_t)(16 * nblk_live + (idx >> 3)) * tok_stride + (idx & 7) * 8) = zero8();
+}
+
 // backward as two launches (VITX_ATTN_BWD_SPLIT=1: the A/B and bit-identity form): dQ (+ row sums D to HBM) ...
 template <int NTP>
 __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
                                                           const bf16_t* __restrict__ d_o, const float* __restrict__ lse,
                                                           float* __restrict__ dsum, bf16_t* __restrict__ dqkv, int n, int h, float scale,
-                                                          const bf16_t* __restrict__ zero_page) {
+                                                          const bf16_t* __restrict__ zero_page, int nq_live) {
   constexpr int NKP = 16 * NTP;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* k_rm = smem;
@@ -439,21 +457,24 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dq_kernel(const bf16_t* 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   const int64_t orow0 = (int64_t)bi * n * inner + hi * DH;
-  for (int qb = wave; qb < (n + 15) / 16; qb += nwaves) {
+  const int nblk_live = (nq_live + 15) / 16;
+  for (int qb = wave; qb < nblk_live; qb += nwaves) {
     const int qi = lane & 15, q = qb * 16 + qi, qc = min(q, n - 1);
     DqOperands x;
     dq_load(x, qbase, tok_stride, o + orow0, d_o + orow0, inner, qb, lane, n);
     const float d = dq_block<NTP>(k_rm, v_rm, x, tok_stride, dqkv + (int64_t)bi * n * tok_stride + hi * DH, qb, lane, n, scale,
-                                  lse[(int64_t)bh * n + qc] * 1.44269504088896340736f);
-    if ((lane >> 4) == 0 && q < n) dsum[(int64_t)bh * n + q] = d;
+                                  lse[(int64_t)bh * n + qc] * 1.44269504088896340736f, nq_live);
+    if ((lane >> 4) == 0 && q < nq_live) dsum[(int64_t)bh * n + q] = d;
   }
+  dq_zero_dead_blocks(dqkv + (int64_t)bi * n * tok_stride + hi * DH, tok_stride, nblk_live, n, tid, (int)blockDim.x);
 }
 
 // ... and dK, dV
 template <int NTP>
 __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ d_o,
                                                            const float* __restrict__ lse, const float* __restrict__ dsum,
-                                                           bf16_t* __restrict__ dqkv, int n, int h, float scale, const bf16_t* __restrict__ zero_page) {
+                                                           bf16_t* __restrict__ dqkv, int n, int h, float scale, const bf16_t* __restrict__ zero_page,
+                                                           int nq_live) {
   constexpr int NQP = 16 * NTP;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* q_rm = smem;
@@ -466,18 +487,18 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_bwd_dkv_kernel(const bf16_t*
   const bf16_t* qbase = qkv + (int64_t)bi * n * tok_stride + hi * DH;
   const int tid = threadIdx.x, lane = tid & 63, nwaves = blockDim.x >> 6;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  stage_head_dma(qbase, tok_stride, n, NQP, q_rm, zero_page, wave, lane, nwaves);
-  stage_head_dma(d_o + (int64_t)bi * n * inner + hi * DH, inner, n, NQP, do_rm, zero_page, wave, lane, nwaves);
+  stage_head_dma(qbase, tok_stride, nq_live, NQP, q_rm, zero_page, wave, lane, nwaves);
+  stage_head_dma(d_o + (int64_t)bi * n * inner + hi * DH, inner, nq_live, NQP, do_rm, zero_page, wave, lane, nwaves);
   for (int i = tid; i < NQP; i += blockDim.x) {
-    lse_s[i] = i < n ? lse[(int64_t)bh * n + i] * 1.44269504088896340736f : 0.f;
-    d_s[i] = i < n ? dsum[(int64_t)bh * n + i] : 0.f;
+    lse_s[i] = i < nq_live ? lse[(int64_t)bh * n + i] * 1.44269504088896340736f : 0.f;
+    d_s[i] = i < nq_live ? dsum[(int64_t)bh * n + i] : 0.f;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   for (int kb = wave; kb < (n + 15) / 16; kb += nwaves) {
     DkvOperands x;
     dkv_load(x, qbase + inner, tok_stride, inner, kb, lane, n);
-    dkv_block<NTP>(q_rm, do_rm, lse_s, d_s, x, tok_stride, inner, dqkv + (int64_t)bi * n * tok_stride + inner + hi * DH, kb, lane, n, scale);
+    dkv_block<NTP>(q_rm, do_rm, lse_s, d_s, x, tok_stride, inner, dqkv + (int64_t)bi * n * tok_stride + inner + hi * DH, kb, lane, n, scale, nq_live);
   }
 }
 
@@ -490,7 +511,7 @@ template <int NTP>
 __global__ __launch_bounds__(ATT_THREADS, 4) void attn_bwd_fused_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
                                                              const bf16_t* __restrict__ d_o, const float* __restrict__ lse,
                                                              bf16_t* __restrict__ dqkv, int n, int h, float scale,
-                                                             const bf16_t* __restrict__ zero_page, int planar) {
+                                                             const bf16_t* __restrict__ zero_page, int planar, int nq_live) {
   constexpr int NKP = 16 * NTP, NQP = 16 * NTP;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* k_rm = smem;                                 // phase 1: K, V      phase 2: Q, dO
@@ -508,39 +529,41 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attn_bwd_fused_kernel(const bf
   stage_head_dma(qbase + inner, tok_stride, n, NKP, k_rm, zero_page, wave, lane, nwaves);
   stage_head_dma(qbase + 2 * inner, tok_stride, n, NKP, v_rm, zero_page, wave, lane, nwaves);
   for (int i = tid; i < NQP; i += blockDim.x) {
-    lse_s[i] = i < n ? lse[(int64_t)bh * n + i] * 1.44269504088896340736f : 0.f;
+    lse_s[i] = i < nq_live ? lse[(int64_t)bh * n + i] * 1.44269504088896340736f : 0.f;
     d_s[i] = 0.f;
   }
   const int64_t orow0 = L.o0;
   const int nblk = (n + 15) / 16;
+  const int nblk_live = (nq_live + 15) / 16;   // query blocks of the dQ pass (nq_live < n: the class-row form of the last block)
   DqOperands xq;
-  if (wave < nblk) dq_load(xq, qbase, tok_stride, o + orow0, d_o + orow0, ostr, wave, lane, n);   // in flight together with the K / V images
+  if (wave < nblk_live) dq_load(xq, qbase, tok_stride, o + orow0, d_o + orow0, ostr, wave, lane, n);   // in flight together with the K / V images
   ATTN_STAMP(0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   ATTN_STAMP(1);
-  for (int qb = wave; qb < nblk; qb += nwaves) {   // ------------------------------------ phase 1: dQ, D
+  for (int qb = wave; qb < nblk_live; qb += nwaves) {   // ------------------------------- phase 1: dQ, D
     const int q = qb * 16 + (lane & 15);
     DqOperands nx;
-    if (qb + nwaves < nblk) dq_load(nx, qbase, tok_stride, o + orow0, d_o + orow0, ostr, qb + nwaves, lane, n);
-    const float d = dq_block<NTP>(k_rm, v_rm, xq, tok_stride, dqkv + L.q0, qb, lane, n, scale, lse_s[min(q, n - 1)]);
-    if ((lane >> 4) == 0 && q < n) d_s[q] = d;      // stays in LDS for phase 2
+    if (qb + nwaves < nblk_live) dq_load(nx, qbase, tok_stride, o + orow0, d_o + orow0, ostr, qb + nwaves, lane, n);
+    const float d = dq_block<NTP>(k_rm, v_rm, xq, tok_stride, dqkv + L.q0, qb, lane, n, scale, lse_s[min(q, n - 1)], nq_live);
+    if ((lane >> 4) == 0 && q < nq_live) d_s[q] = d;      // stays in LDS for phase 2
     xq = nx;
   }
+  dq_zero_dead_blocks(dqkv + L.q0, tok_stride, nblk_live, n, tid, (int)blockDim.x);
   DkvOperands xk;
   if (wave < nblk) dkv_load(xk, qbase + inner, tok_stride, inner, wave, lane, n);   // L2 hits, in flight across the barrier and the restaging
   ATTN_STAMP(2);
   __syncthreads();               // every wave is done with the K / V images; D is complete
   ATTN_STAMP(3);
-  stage_head_dma(qbase, tok_stride, n, NQP, q_rm, zero_page, wave, lane, nwaves);
-  stage_head_dma(d_o + orow0, ostr, n, NQP, do_rm, zero_page, wave, lane, nwaves);
+  stage_head_dma(qbase, tok_stride, nq_live, NQP, q_rm, zero_page, wave, lane, nwaves);   // rows >= nq_live: the zero page
+  stage_head_dma(d_o + orow0, ostr, nq_live, NQP, do_rm, zero_page, wave, lane, nwaves);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   ATTN_STAMP(4);
   for (int kb = wave; kb < nblk; kb += nwaves) {   // ------------------------------------ phase 2: dK, dV
     DkvOperands nx;
     if (kb + nwaves < nblk) dkv_load(nx, qbase + inner, tok_stride, inner, kb + nwaves, lane, n);
-    dkv_block<NTP>(q_rm, do_rm, lse_s, d_s, xk, tok_stride, inner, dqkv + L.q0 + inner, kb, lane, n, scale);
+    dkv_block<NTP>(q_rm, do_rm, lse_s, d_s, xk, tok_stride, inner, dqkv + L.q0 + inner, kb, lane, n, scale, nq_live);
     xk = nx;
   }
   ATTN_STAMP(5);
@@ -575,20 +598,23 @@ bool attn_bf16_supported(int n, int dim_head) { return dim_head == DH && n >= 1 
 
 int vitx_attn_probe_planar = 0;   // tools/probe_attn sets it (layout 1 of AttnLayout); the engine's tensors are layout 0
 
-void launch_attn_bf16_fwd(const bf16_t* qkv, bf16_t* o, float* lse, int b, int n, int h, float scale, const bf16_t* zero_page, int reverse, hipStream_t s) {
+void launch_attn_bf16_fwd(const bf16_t* qkv, bf16_t* o, float* lse, int b, int n, int h, float scale, const bf16_t* zero_page, int reverse, hipStream_t s,
+                          int nq_live) {
+  if (nq_live <= 0 || nq_live > n) nq_live = n;
   const int ntp = pick_ntp(n);
   const int nkp = 16 * ntp;
   const int smem = 2 * nkp * ROWB;
   // (image, head) tasks from the last to the first: qkv (232 MB at ViT-B/16, written front to back by the GEMM before) is read newest rows
   // first, while they are still in the 256 MB memory-side cache (1.24 -> 1.15 ms per step); `reverse` = bit 4 of the engine's reverse_mask
   // (VITX_REVERSE, read once per handle)
-#define CALL(NTP) { set_smem(attn_fwd_kernel<NTP>, smem); hipLaunchKernelGGL(attn_fwd_kernel<NTP>, dim3(b * h), dim3(att_threads(n)), smem, s, qkv, o, lse, n, h, scale, zero_page, reverse, vitx_attn_probe_planar); }
+#define CALL(NTP) { set_smem(attn_fwd_kernel<NTP>, smem); hipLaunchKernelGGL(attn_fwd_kernel<NTP>, dim3(b * h), dim3(att_threads(n)), smem, s, qkv, o, lse, n, h, scale, zero_page, reverse, vitx_attn_probe_planar, nq_live); }
   VITX_NTP_DISPATCH(ntp, CALL);
 #undef CALL
 }
 
 void launch_attn_bf16_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o, const float* lse, float* dsum_ws, bf16_t* dqkv, int b,
-                          int n, int h, float scale, const bf16_t* zero_page, hipStream_t s) {
+                          int n, int h, float scale, const bf16_t* zero_page, hipStream_t s, int nq_live) {
+  if (nq_live <= 0 || nq_live > n) nq_live = n;
   const int ntp = pick_ntp(n);
   const int np = 16 * ntp;
   const int smem_dq = 2 * np * ROWB;
@@ -596,7 +622,7 @@ void launch_attn_bf16_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o,
   const char* split_env = vitx_env("VITX_ATTN_BWD_SPLIT");   // A/B and the bit-identity test: the two-launch form (read per call)
   const bool split = split_env && atoi(split_env) != 0;
   if (!split) {
-#define CALLF(NTP) { set_smem(attn_bwd_fused_kernel<NTP>, smem_dkv); hipLaunchKernelGGL(attn_bwd_fused_kernel<NTP>, dim3(b * h), dim3(att_threads(n)), smem_dkv, s, qkv, o, d_o, lse, dqkv, n, h, scale, zero_page, vitx_attn_probe_planar); }
+#define CALLF(NTP) { set_smem(attn_bwd_fused_kernel<NTP>, smem_dkv); hipLaunchKernelGGL(attn_bwd_fused_kernel<NTP>, dim3(b * h), dim3(att_threads(n)), smem_dkv, s, qkv, o, d_o, lse, dqkv, n, h, scale, zero_page, vitx_attn_probe_planar, nq_live); }
     VITX_NTP_DISPATCH(ntp, CALLF);
 #undef CALLF
     return;
@@ -605,8 +631,8 @@ void launch_attn_bf16_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o,
   {                                                                                                                                \
     set_smem(attn_bwd_dq_kernel<NTP>, smem_dq);                                                                                    \
     set_smem(attn_bwd_dkv_kernel<NTP>, smem_dkv);                                                                                  \
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<NTP>, dim3(b * h), dim3(att_threads(n)), smem_dq, s, qkv, o, d_o, lse, dsum_ws, dqkv, n, h, scale, zero_page);   \
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<NTP>, dim3(b * h), dim3(att_threads(n)), smem_dkv, s, qkv, d_o, lse, dsum_ws, dqkv, n, h, scale, zero_page);    \
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<NTP>, dim3(b * h), dim3(att_threads(n)), smem_dq, s, qkv, o, d_o, lse, dsum_ws, dqkv, n, h, scale, zero_page, nq_live);   \
+    hipLaunchKernelGGL(attn_bwd_dkv_kernel<NTP>, dim3(b * h), dim3(att_threads(n)), smem_dkv, s, qkv, d_o, lse, dsum_ws, dqkv, n, h, scale, zero_page, nq_live);    \
   }
   VITX_NTP_DISPATCH(ntp, CALL);
 #undef CALL

@@ -814,6 +814,13 @@ int32_t vitx_debug_read(vitx_handle h, const char* which, int32_t layer, float* 
   const void* src = nullptr;
   int64_t rows = 0, cols = 0, ld = 0;
   bool is_t = false;
+  if (w == "last_block_form") {   // 1: the last forward ran its last block on the class rows only (engine.hip, cls_rows_apply); 0: on every row
+    if (n_elems) *n_elems = 1;
+    if (!out_host) return VITX_OK;
+    if (cap < 1) return fail(VITX_ERR_INVALID, "output buffer too small");
+    out_host[0] = (h->have_fwd && h->last_cls_only) ? 1.f : 0.f;
+    return VITX_OK;
+  }
   if (w == "pooled_ln") { src = h->yh; rows = b; cols = ld = c.dim; is_t = true; }
   else if (w == "logits") { src = h->logits; rows = b; cols = c.num_classes; ld = h->nc_k; }
   else if (w == "dlogits") { src = h->dlogits; rows = b; cols = c.num_classes; ld = h->nc_k; }
@@ -822,6 +829,12 @@ int32_t vitx_debug_read(vitx_handle h, const char* which, int32_t layer, float* 
     if (!st) return fail(VITX_ERR_INVALID, "layer out of range");
     if (c.variant == VITX_VARIANT_CAIT) { nq = st->nq_max == 1 ? 1 : h->last_np; nk = st->nq_max == 1 ? 1 + h->last_np : h->last_np; }
     BlockActs& ba = st->ba[(size_t)l];
+    // after a class-row forward the last block holds its activations behind qkv for the class rows only: complete it first (same bits on those rows)
+    if (h->last_cls_only && st == &h->stages[0] && l == st->depth - 1 && w != "x_in" && w != "embed" && w != "y1" && w != "qkv") {
+      std::string err;
+      const int rc = engine_complete_last_block(h, err);
+      if (rc != VITX_OK) return fail(rc, err);
+    }
     rows = (int64_t)b * nq;
     if (w == "x_in" || w == "embed") { src = ba.x_in; cols = ld = c.dim; }
     else if (w == "x_mid") { src = ba.x_mid; cols = ld = c.dim; }

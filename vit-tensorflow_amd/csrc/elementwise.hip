@@ -518,6 +518,15 @@ __global__ void set_token_row_kernel(float* __restrict__ x, const float* __restr
   const int c = (int)(e - bi * d);
   x[(bi * ntok + row) * d + c] = tok[c];
 }
+// dst[r][:] = src[r][:] in 16-B chunks, rows at independent strides (counted in chunks): class row of every image -> compact rows and back
+__global__ void copy_rows_kernel(const uint4* __restrict__ src, int64_t src_stride, uint4* __restrict__ dst, int64_t dst_stride, int rows, int row_chunks) {
+  const int64_t total = (int64_t)rows * row_chunks;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = e / row_chunks;
+    const int c = (int)(e - r * row_chunks);
+    dst[r * dst_stride + c] = src[r * src_stride + c];
+  }
+}
 __global__ void mean_pool_kernel(const float* __restrict__ x, int b, int ntok, int d, float* __restrict__ out, int stride_tok) {
   const int64_t total = (int64_t)b * d;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
@@ -1007,6 +1016,12 @@ void launch_to_f32(const void* in, int in_bf16, int64_t ldi, float* out, int64_t
 }
 void launch_set_token_row(float* x, const float* tok, int b, int ntok, int row, int d, hipStream_t s) {
   hipLaunchKernelGGL(set_token_row_kernel, dim3((unsigned)ceil_div((int64_t)b * d, 256)), dim3(256), 0, s, x, tok, b, ntok, row, d);
+}
+void launch_copy_rows(const void* src, int64_t src_stride_bytes, void* dst, int64_t dst_stride_bytes, int rows, int row_bytes, hipStream_t s) {
+  const int64_t total = (int64_t)rows * (row_bytes / 16);
+  if (total == 0) return;
+  hipLaunchKernelGGL(copy_rows_kernel, dim3(grid_for(total)), dim3(256), 0, s, (const uint4*)src, src_stride_bytes / 16, (uint4*)dst, dst_stride_bytes / 16, rows,
+                     row_bytes / 16);
 }
 void launch_mean_pool(const float* x, int b, int ntok, int d, float* out, hipStream_t s, int stride_tok) {
   hipLaunchKernelGGL(mean_pool_kernel, dim3(grid_for((int64_t)b * d)), dim3(256), 0, s, x, b, ntok, d, out, stride_tok ? stride_tok : ntok);

@@ -89,6 +89,15 @@ struct BlockActs {
   int par_first = 0, par_last = 0;   // backward order inside a group of parallel half-blocks: first / last one processed (1 + 1 = alone)
 };
 
+// Class-row form of the last block (engine.hip, block_forward_cls_rows): under cls pooling the head reads row 0 of every image only, so everything of
+// the last block behind its attention runs on the b class rows, gathered into these compact [b, *] buffers.  The bf16 ones are A / K operands of
+// GEMMs and obey the row-padding invariant (round_up(max_batch, 256) + 320 rows, rows >= b zero: registered with the T buffers).
+struct ClsRows {
+  void *o = nullptr, *y2 = nullptr, *hpre = nullptr, *act = nullptr;                      // forward, kept for the backward: [b, inner | d | m | m]
+  float *x_mid = nullptr, *x_out = nullptr, *mean2 = nullptr, *rstd2 = nullptr;           // fp32 [b, d] residual stream, LayerNorm 2 statistics
+  void *g_lp = nullptr, *g_lp2 = nullptr, *d_h = nullptr, *d_y = nullptr, *d_o = nullptr; // backward: bf16 residual gradient in front of / behind the MLP branch, d(hpre), d(y2), d(o)
+};
+
 struct Stage {
   std::string prefix;
   int depth = 0;
@@ -192,6 +201,11 @@ struct vitx_engine {
   float *opt_m = nullptr, *opt_v = nullptr; int opt_step = 0;   // optimizer state (allocated on first use)
   bf16_t *bench_a = nullptr, *bench_b = nullptr; float* bench_c = nullptr; int64_t bench_elems = 0;
 
+  // class-row form of the last block
+  ClsRows cr;
+  bool cls_rows_ok = false;          // the handle's configuration allows it (buffers exist); the per-call conditions are checked by every engine_forward
+  bool last_cls_only = false;        // the last engine_forward ran it: the last block's saved activations behind qkv are the compact ones
+
   // state of the last forward
   bool have_fwd = false;
   bool have_tf = false;              // saved activations describe a transformer_forward(tokens) of [tf_b, tf_n, dim]
@@ -275,6 +289,9 @@ int engine_forward(vitx_engine* e, const float* img_dev, int b, int H, int W, in
 // d_distill_dev [b, dim]: cotangent of distill_out; d_token_out_dev [dim]: gradient of the distillation token
 int engine_backward(vitx_engine* e, const float* dlogits_dev, float* dimg_dev, std::string& err, const float* d_distill_dev = nullptr,
                     float* d_token_out_dev = nullptr);
+// after a class-row forward: runs the last block again on every row from its saved input (same bits on the class rows) and clears the flag, so that
+// every saved activation of that block exists and a later backward takes the full form (vitx_debug_read)
+int engine_complete_last_block(vitx_engine* e, std::string& err);
 int engine_transformer_forward(vitx_engine* e, const float* tokens_dev, int b, int n, int training, uint64_t seed, float* out_dev, std::string& err);
 int engine_transformer_backward(vitx_engine* e, const float* dout_dev, float* dtokens_dev, std::string& err);
 int engine_patch_tokens_forward(vitx_engine* e, const float* img_dev, int b, int H, int W, float* tokens_dev, float* patches_f32_dev_or_null,

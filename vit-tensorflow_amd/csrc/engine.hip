@@ -1011,11 +1011,88 @@ static bool use_fused_attn_x3(const vitx_engine* e, int n) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// class-row form of the last block (vit.py:170: `x[:, 0]` is all the head reads under pool = 'cls')
+// ------------------------------------------------------------------------------------------------
+// The out-projection, the second LayerNorm and the MLP are row-wise: rows of the last block's output that nothing reads need not be computed, and their
+// cotangents are exact zeros.  Forward: LayerNorm 1 and the qkv Dense run on every row (K and V of every token feed the class query), the attention
+// computes query row 0 of every image, and everything behind it runs on the b class rows, gathered into compact buffers (ClsRows).  Every Dense adds
+// its K terms in the same order whatever M is, so the logits have the bits of the full form.  VITX_LAST_BLOCK_FULL=1 (read per forward) keeps the
+// full form.
+static bool cls_rows_apply(const vitx_engine* e, int ntok, int extra, float drop) {
+  if (!e->cls_rows_ok || extra || drop > 0.f || !use_fused_attn(e, ntok)) return false;
+  return !vitx_env_flag("VITX_LAST_BLOCK_FULL");
+}
+// fc1 + GELU of the b class rows, with the GELU rounding the full launch gives exactly those rows.  The epilogue is not the same function of the
+// accumulator everywhere: interior 256 x 256 tiles of variant 13 read GELU and its derivative from the LDS table, every other tile (and variant)
+// evaluates the polynomial.  In the launch over all b * nq rows the class row of image i is row i * nq: the images whose row lies in an interior tile
+// go out as one launch of variant 13 on whole tiles (the compact rows >= b are zero: rows up to the tile end are computed and cleared again), the
+// others as a launch of the 128 x 128 tile, which has no table.
+static void cls_fc1_fwd(vitx_engine* e, const Dense& w, int b, int nq) {
+  ClsRows& cr = e->cr;
+  const int d = e->cfg.dim, m = e->cfg.mlp_dim;
+  const int shared = comm_busy(e);
+  const int64_t rows_full = (int64_t)b * nq;
+  int vfull = e->gemm_kernel & 15;
+  if (vfull == 0) vfull = gemm_bf16_variant_for(EPI_BIAS_GELU, (int)rows_full, w.out, w.in_k, 0, shared);
+  int ntab = 0;   // images [0, ntab): table form
+  if (vfull == 13 && gemm_bf16_gelu_table_active()) ntab = (int)std::min<int64_t>(b, ceil_div(rows_full / 256 * 256, nq));
+  auto launch = [&](int r0, int rows, int kernel) {
+    EpiParams ep;
+    ep.out = boff(cr.hpre, (int64_t)r0 * m, 2); ep.ldo = m; ep.out2 = boff(cr.act, (int64_t)r0 * m, 2); ep.ldo2 = m;
+    ep.nt_out = e->nt_mask & 1;
+    ep.M = rows; ep.N = w.out; ep.bias = dense_b(e, w); ep.zero_pad = 1;
+    finalize_epi(ep);
+    Bf16GemmArgs g;
+    g.A = (const bf16_t*)cr.y2 + (int64_t)r0 * d; g.lda = d;
+    g.B = w.wt; g.ldb = w.in_k;
+    g.M = rows; g.N = w.out; g.K = w.in_k; g.kernel = kernel; g.shared_gpu = shared;
+    char shape[48];
+    if (e->profiling) snprintf(shape, sizeof shape, "shape nt e%d %dx%dx%d", (int)EPI_BIAS_GELU, g.M, g.N, g.K);
+    Prof pr(e, "gemm_bf16_mfma", 2.0 * rows * (double)w.out * w.in, dense_launch_bytes(e, EPI_BIAS_GELU, ep, rows, w.in, w.out), e->profiling ? shape : nullptr);
+    launch_gemm_bf16(g, ep, EPI_BIAS_GELU, e->stream);
+  };
+  const int mpad = (int)round_up(ntab, 256);
+  if (ntab > 0) launch(0, mpad, 13);
+  if (ntab < b) launch(ntab, b - ntab, 1);
+  if (mpad > b) {   // rows >= b of act are K padding of the fc2 weight gradient
+    launch_fill_zero(boff(cr.hpre, (int64_t)b * m, 2), (int64_t)(mpad - b) * m * 2, e->stream);
+    launch_fill_zero(boff(cr.act, (int64_t)b * m, 2), (int64_t)(mpad - b) * m * 2, e->stream);
+  }
+}
+
+// behind the attention (query row 0 of every image in ba.o): out-projection + residual, LayerNorm 2, fc1 + GELU, fc2 + residual on b rows
+static void block_forward_cls_rows(vitx_engine* e, const BlockParams& bp, const BlockActs& ba, int b, int nq) {
+  const vitx_config& c = e->cfg;
+  const int d = c.dim, inner = e->inner, m = c.mlp_dim;
+  ClsRows& cr = e->cr;
+  {
+    Prof pr(e, "cls_rows", 0, (double)b * inner * 4);
+    launch_copy_rows(ba.o, (int64_t)nq * inner * 2, cr.o, (int64_t)inner * 2, b, inner * 2, e->stream);
+  }
+  {
+    EpiParams ep;
+    ep.out = cr.x_mid; ep.ldo = d; ep.resid = ba.x_in; ep.ldr = (int64_t)nq * d;   // the residual input: row 0 of every image, in place
+    dense_fwd(e, cr.o, inner, b, bp.out, EPI_BIAS_RESID, ep);
+  }
+  {
+    Prof pr(e, "layernorm_fwd", 0, (double)b * d * 6);
+    launch_layernorm_fwd(cr.x_mid, d, e->params + bp.ln2_g, e->params + bp.ln2_b, cr.y2, 1, d, cr.mean2, cr.rstd2, b, d, c.ln_eps, e->stream);
+  }
+  cls_fc1_fwd(e, bp.fc1, b, nq);
+  {
+    EpiParams ep;
+    ep.out = cr.x_out; ep.ldo = d; ep.resid = cr.x_mid; ep.ldr = d;
+    dense_fwd(e, cr.act, m, b, bp.fc2, EPI_BIAS_RESID, ep);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // one transformer block: x = attn(LN(x)) [*scale] + x ; x = mlp(LN(x)) [*scale] + x
 //   (vit.py:99-104, deepvit.py:106-110, cait.py:146-153)
 // ------------------------------------------------------------------------------------------------
+// cls_rows: the class-row form (last block of a cls-pooled ViT; the caller has checked cls_rows_apply)
 static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq, int nc, const float* context, float drop, uint64_t seed,
-                         std::string& err) {
+                         std::string& err, bool cls_rows = false) {
   const uint32_t site0 = (uint32_t)((si * 1000 + l) * 4);
   const BlockParams& bp = st.bp[l];
   BlockActs& ba = st.ba[l];
@@ -1069,8 +1146,11 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
     Prof pr(e, "attn_x3_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
     launch_attn_x3_fwd((const float*)ba.qkv, (float*)ba.o, ba.lse, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), e->stream);
   } else if (use_fused_attn(e, nq)) {
-    Prof pr(e, "attn_bf16_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
-    launch_attn_bf16_fwd((const bf16_t*)ba.qkv, (bf16_t*)ba.o, ba.lse, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), (const bf16_t*)e->zero_page, (e->reverse_mask >> 2) & 1, e->stream);
+    // (class-row form: one live query row per image -- q / o traffic and the products of one row, k and v of every row)
+    const double live = cls_rows ? 1.0 / nq : 1.0;
+    Prof pr(e, "attn_bf16_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head * live, (double)rows * inner * (2 + 2 * live) * esz);
+    launch_attn_bf16_fwd((const bf16_t*)ba.qkv, (bf16_t*)ba.o, ba.lse, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), (const bf16_t*)e->zero_page, (e->reverse_mask >> 2) & 1, e->stream,
+                         cls_rows ? 1 : 0);
   } else {
     const int need = c.variant == VITX_VARIANT_VIT ? 1 : 3;
     if (e->keep_scores && ba.sc_keep_elems == 0) {   // first use: this block's own score buffers, sized for the largest call
@@ -1091,6 +1171,10 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
       if (rc != VITX_OK) return rc;
     }
     attn_generic_fwd(e, bp, av, b, keep ? &ba : nullptr);
+  }
+  if (cls_rows) {
+    block_forward_cls_rows(e, bp, ba, b, nq);
+    return VITX_OK;
   }
   if (bp.has_out && drop > 0.f) {
     // Dense -> Dropout -> (LayerScale) -> + residual, unfused (vit.py:61-69,83,101)
@@ -1153,11 +1237,65 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
   return VITX_OK;
 }
 
+// Class-row form, backward of everything behind the attention.  On entry e->g holds d(x_out): the head's gradient on the class rows, zeros elsewhere.  The
+// VJPs of fc2, fc1, LayerNorm 2 and the out-projection run on the b class rows; on exit the class rows of e->g hold the residual gradient in front of
+// the MLP branch (the other rows stay zero) and the class rows of e->d_o hold d(attention output) -- the only rows of it the restricted attention
+// backward reads.  A weight gradient over b token rows is a single K slice at the batches in use: written in place, no partials.
+static void block_backward_cls_rows(vitx_engine* e, const BlockParams& bp, int b, int nq) {
+  const vitx_config& c = e->cfg;
+  const int d = c.dim, inner = e->inner, m = c.mlp_dim;
+  ClsRows& cr = e->cr;
+  {
+    Prof pr(e, "cls_rows", 0, (double)b * d * 6);
+    launch_extract_rows(e->g, b, nq, 0, 1, d, cr.g_lp, 1, d, e->stream);   // bf16 copy of the class rows of the residual gradient
+  }
+  // ---- MLP branch (same order as the full form: producer of d hpre, its two consumers, the fc2 weight gradient, the LayerNorm VJP)
+  const bool fc1_bias_fused = !(e->gemm_kernel & 256) && bp.fc1.b >= 0;
+  const int cs_rows = (int)ceil_div(b, 96);
+  {
+    EpiParams ep; ep.out = cr.d_h; ep.ldo = m; ep.aux = cr.hpre; ep.ldaux = m;
+    if (fc1_bias_fused) {
+      launch_fill_zero(e->red_ws, (int64_t)cs_rows * m * 4, e->stream);
+      ep.colsum = e->red_ws; ep.ldcs = m;
+    }
+    dense_dgrad(e, cr.g_lp, d, b, bp.fc2, EPI_GELU_BWD, ep);
+    if (fc1_bias_fused) {
+      Prof pr(e, "reduce_partials", 0, (double)(cs_rows + 1) * m * 4);
+      launch_reduce_partials3(e->red_ws, cs_rows, m, m, 1, e->grads + bp.fc1.b, nullptr, nullptr, e->red_ws + (int64_t)cs_rows * m, 1.0f, e->stream);
+    }
+  }
+  {
+    EpiParams ep; ep.out = cr.d_y; ep.ldo = d;
+    dense_dgrad(e, cr.d_h, m, b, bp.fc1, EPI_STORE, ep);
+  }
+  dense_wgrad(e, cr.y2, d, cr.d_h, m, b, bp.fc1);
+  if (!fc1_bias_fused) bias_grad(e, cr.d_h, 1, m, b, bp.fc1);
+  dense_wgrad(e, cr.act, m, cr.g_lp, d, b, bp.fc2);
+  {
+    // in place on the class rows of e->g (row stride nq * d); the fc2 bias gradient = column sums of the incoming class rows
+    Prof pr(e, "layernorm_bwd", 0, (double)b * d * 16);
+    launch_layernorm_bwd(cr.d_y, 1, d, cr.x_mid, d, cr.mean2, cr.rstd2, e->params + bp.ln2_g, e->g, (int64_t)nq * d, e->g, (int64_t)nq * d, cr.g_lp2, d,
+                         e->red_ws, e->grads + bp.ln2_g, e->grads + bp.ln2_b, dense_gb(e, bp.fc2), b, d, e->stream);
+  }
+  // ---- out-projection (its bias gradient = column sums of e->g: on the LayerNorm 1 VJP, as in the full form)
+  {
+    EpiParams ep; ep.out = cr.d_o; ep.ldo = inner;
+    dense_dgrad(e, cr.g_lp2, d, b, bp.out, EPI_STORE, ep);
+  }
+  dense_wgrad(e, cr.o, inner, cr.g_lp2, d, b, bp.out);
+  {
+    Prof pr(e, "cls_rows", 0, (double)b * inner * 4);
+    launch_copy_rows(cr.d_o, (int64_t)inner * 2, e->d_o, (int64_t)nq * inner * 2, b, inner * 2, e->stream);
+  }
+}
+
 // g (fp32 [rows,d]) holds dL/dx_out on entry and dL/dx_in on exit; g_lp is its T copy (bf16 mode).
 static inline int64_t branch_key(int si, int l, int mlp) { return (((int64_t)si + 1) << 32) | ((int64_t)l << 1) | mlp; }
 // next_l: the layer of the same stage (same token rows) whose backward runs right after this one, or -1 -- lets this block's last LayerNorm VJP carry
 // the LayerScale VJP of that layer's MLP branch (block_layernorm_bwd, NextBranch)
-static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int nq, int nc, float drop, uint64_t seed, std::string& err, int next_l = -1) {
+// cls_rows: the class-row form (the forward of this block ran it: e->last_cls_only)
+static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int nq, int nc, float drop, uint64_t seed, std::string& err, int next_l = -1,
+                          bool cls_rows = false) {
   const uint32_t site0 = (uint32_t)((si * 1000 + l) * 4);
   const BlockParams& bp = st.bp[l];
   BlockActs& ba = st.ba[l];
@@ -1188,7 +1326,9 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
   const void* dbranch = gT;
   bool fc2_bias_done = false, out_bias_done = false;   // bias gradient already produced by the LayerScale VJP pass
   const int64_t key_mlp = branch_key(si, l, 1), key_attn = branch_key(si, l, 0);
-  if (!ba.skip_mlp) {
+  if (cls_rows) {
+    block_backward_cls_rows(e, bp, b, nq);
+  } else if (!ba.skip_mlp) {
   // ---- MLP branch: x_out = x_mid + scale * fc2(gelu(fc1(LN(x_mid))))
   if (e->dbr_ready == key_mlp) {           // the LayerNorm VJP of the layer above has already run this branch's LayerScale VJP (block_layernorm_bwd, nb)
     e->dbr_ready = 0;
@@ -1305,7 +1445,10 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
   }
   bool out_bias_in_ln = false;
   const void* d_o = dbranch;   // when to_out is the identity (vit.py:53) the branch gradient IS d(attn_out)
-  if (bp.has_out) {
+  if (cls_rows) {
+    out_bias_in_ln = true;
+    d_o = e->d_o;
+  } else if (bp.has_out) {
     EpiParams ep; ep.out = e->d_o; ep.ldo = inner;
     const hipEvent_t fork_out = side_prefork(e);   // o and the branch gradient are complete
     dense_dgrad(e, dbranch, d, rows, bp.out, EPI_STORE, ep);
@@ -1389,9 +1532,11 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
       launch_attn_x3_bwd((const float*)ba.qkv, (const float*)ba.o, (const float*)d_o, ba.lse, (float*)e->d_qkv, b, nq, c.heads,
                          1.0f / std::sqrt((float)c.dim_head), e->stream);
     } else if (use_fused_attn(e, nq)) {
-      Prof pr(e, "attn_bf16_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
+      // (class-row form: q, o, dO of one row per image; k, v read and d(q, k, v) written for every row)
+      const double live = cls_rows ? 1.0 / nq : 1.0;
+      Prof pr(e, "attn_bf16_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head * live, (double)rows * inner * (5 + 3 * live) * esz);
       launch_attn_bf16_bwd((const bf16_t*)ba.qkv, (const bf16_t*)ba.o, (const bf16_t*)d_o, ba.lse, e->dsum, (bf16_t*)e->d_qkv, b, nq,
-                           c.heads, 1.0f / std::sqrt((float)c.dim_head), (const bf16_t*)e->zero_page, e->stream);
+                           c.heads, 1.0f / std::sqrt((float)c.dim_head), (const bf16_t*)e->zero_page, e->stream, cls_rows ? 1 : 0);
     } else {
       int rc = ensure_scores(e, 4, (int64_t)b * c.heads * nq * round_up(nk, 4), err);
       if (rc != VITX_OK) return rc;
@@ -1777,6 +1922,26 @@ static int engine_create_body(vitx_engine* e, const vitx_config& cfg, std::strin
     if ((rc = ring(e->rg_cs, e->cs_part, cs_bytes, 4)) != VITX_OK) return rc;
   }
   DALLOC(e->dsum, (size_t)B * c.heads * e->ntok_cap * 4 + 16, false);
+  // class-row form of the last block (block_forward_cls_rows): what the configuration must allow; the per-call conditions are in cls_rows_apply
+  e->cls_rows_ok = e->bf16 && c.variant == VITX_VARIANT_VIT && c.pool == VITX_POOL_CLS && nbranch == 1 && !c.small_dataset && !c.cct_block && !c.nest_block &&
+                   c.depth > 0 && e->stages[0].bp.back().has_out && !e->force_generic_gemm && !e->wgrad_via_transpose;
+  if (e->cls_rows_ok) {
+    ClsRows& cr = e->cr;
+    // activations / gradients only: the bf16 ones are re-zeroed with the other T buffers when the batch geometry changes (rows >= b are K padding)
+    DALLOC(cr.o, (size_t)e->bp * inner * 2, true);
+    DALLOC(cr.y2, (size_t)e->bp * d * 2, true);
+    DALLOC(cr.hpre, (size_t)e->bp * m * 2, true);
+    DALLOC(cr.act, (size_t)e->bp * m * 2, true);
+    DALLOC(cr.g_lp, (size_t)e->bp * d * 2, true);
+    DALLOC(cr.g_lp2, (size_t)e->bp * d * 2, true);
+    DALLOC(cr.d_h, (size_t)e->bp * m * 2, true);
+    DALLOC(cr.d_y, (size_t)e->bp * d * 2, true);
+    DALLOC(cr.d_o, (size_t)e->bp * inner * 2, true);
+    DALLOC(cr.x_mid, (size_t)e->bp * d * 4, false);
+    DALLOC(cr.x_out, (size_t)e->bp * d * 4, false);
+    DALLOC(cr.mean2, (size_t)e->bp * 4, false);
+    DALLOC(cr.rstd2, (size_t)e->bp * 4, false);
+  }
   if (c.small_dataset) {
     e->spt_g = find_param(e, "patch_embedding.norm.gamma");
     e->spt_b = find_param(e, "patch_embedding.norm.beta");
@@ -2007,6 +2172,7 @@ int engine_forward(vitx_engine* e, const float* img_dev, int b, int H, int W, in
   const int np = (H / c.patch_h) * (W / c.patch_w);
   const int ntok = no_cls ? np : np + 1 + extra;
   const int d = c.dim, T = e->bf16;
+  e->last_cls_only = false;   // decided anew by every forward (below)
   ensure_geometry(e, b, ntok);
   if (e->params_dirty) engine_refresh_weights(e);
   Stage& s0 = e->stages[0];
@@ -2042,6 +2208,7 @@ int engine_forward(vitx_engine* e, const float* img_dev, int b, int H, int W, in
     launch_dropout(x0, 0, (int64_t)b * ntok * d, emb_drop, seed, 0u, e->stream);                           // vit.py:166
   }
   draw_layer_dropout(e, seed);
+  const bool cls_rows = cls_rows_apply(e, ntok, extra, drop);   // the last block on the class rows only
   int rc;
   for (int l = 0; l < s0.depth; ++l) {
     if (!e->layer_kept[0][(size_t)l]) {   // cait.py:17-31,147: the whole block is skipped
@@ -2049,7 +2216,7 @@ int engine_forward(vitx_engine* e, const float* img_dev, int b, int H, int W, in
       continue;
     }
     const bool merged = merger && e->merge_after >= 0 && l > e->merge_after;
-    if ((rc = block_forward(e, s0, 0, l, b, merged ? e->merge_t : ntok, 0, nullptr, drop, seed, err)) != VITX_OK) return rc;
+    if ((rc = block_forward(e, s0, 0, l, b, merged ? e->merge_t : ntok, 0, nullptr, drop, seed, err, cls_rows && l == s0.depth - 1)) != VITX_OK) return rc;
     if (merger && l == e->merge_after) merger_forward(e, s0.ba[l].x_out, b, ntok);      // vit_with_patch_merger.py:131-132
   }
   const float* x_last = s0.depth > 0 ? s0.ba[s0.depth - 1].x_out : x0;
@@ -2075,14 +2242,26 @@ int engine_forward(vitx_engine* e, const float* img_dev, int b, int H, int W, in
     x_last = s1.depth > 0 ? s1.ba[s1.depth - 1].x_out : xc;
     head_tok = 1;
   }
+  if (cls_rows) {   // the compact class rows of the last block's output: one row per image
+    x_last = e->cr.x_out;
+    head_tok = 1;
+  }
   if (extra && distill_out_dev)   // x, distill_tokens = x[:, :-1], x[:, -1]  (distill.py:33)
     HIPCHK(hipMemcpy2DAsync(distill_out_dev, (size_t)d * 4, x_last + (int64_t)(ntok - 1) * d, (size_t)ntok * d * 4, (size_t)d * 4, b, hipMemcpyDeviceToDevice, e->stream));
   if ((rc = head_forward(e, x_last, b, head_tok, cait ? 0 : extra, logits_dev, err)) != VITX_OK) return rc;
   e->last_extra = extra;
+  e->last_cls_only = cls_rows;
   e->have_fwd = true;
   e->have_tf = false;
   e->last_b = b; e->last_np = np; e->last_ntok = ntok; e->last_H = H; e->last_W = W; e->last_training = training; e->last_seed = seed;
   return VITX_OK;
+}
+
+int engine_complete_last_block(vitx_engine* e, std::string& err) {
+  if (!e->have_fwd || !e->last_cls_only) return VITX_OK;
+  Stage& s0 = e->stages[0];
+  e->last_cls_only = false;
+  return block_forward(e, s0, 0, s0.depth - 1, e->last_b, e->last_ntok, 0, nullptr, 0.f, e->last_seed, err, false);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2125,7 +2304,7 @@ int engine_embed_forward(vitx_engine* e, const float* img_dev, int b, int H, int
   ep.out = tokens_dev; ep.ldo = d; ep.pos = e->params + e->pos; ep.ldr = d;
   ep.np = np; ep.ntok = ntok; ep.tok_off = 1;
   dense_fwd(e, e->patches, e->pd_k, b * np, e->patch, EPI_PATCH, ep);                                       // efficient.py:24 (+44-45)
-  e->have_fwd = false;          // e->patches no longer describes a full forward
+  e->have_fwd = false; e->last_cls_only = false;          // e->patches no longer describes a full forward
   e->have_embed = true;
   e->last_b = b; e->last_np = np; e->last_ntok = ntok; e->last_H = H; e->last_W = W; e->last_training = 0; e->last_extra = 0;
   return VITX_OK;
@@ -2152,7 +2331,7 @@ int engine_spt_forward(vitx_engine* e, const float* img_dev, int b, int H, int W
   EpiParams ep;
   ep.out = tokens_dev; ep.ldo = c.dim;
   dense_fwd(e, e->patches, e->pd_k, b * np, e->patch, EPI_STORE_F32, ep);
-  e->have_fwd = false; e->have_embed = false;   // e->patches no longer describes a forward that can be differentiated
+  e->have_fwd = false; e->last_cls_only = false; e->have_embed = false;   // e->patches no longer describes a forward that can be differentiated
   return VITX_OK;
 }
 
@@ -2168,7 +2347,7 @@ int engine_patch_dense_forward(vitx_engine* e, const float* patches_dev, int row
   EpiParams ep;
   ep.out = out_dev; ep.ldo = c.dim;
   dense_fwd(e, e->patches, e->pd_k, rows, e->patch, EPI_STORE_F32, ep);
-  e->have_fwd = false; e->have_embed = false;   // e->patches no longer describes a forward that can be differentiated
+  e->have_fwd = false; e->last_cls_only = false; e->have_embed = false;   // e->patches no longer describes a forward that can be differentiated
   return VITX_OK;
 }
 
@@ -2176,7 +2355,7 @@ int engine_head_forward(vitx_engine* e, const float* x_dev, int b, int n, float*
   const vitx_config& c = e->cfg;
   int rc;
   if (b <= 0 || b > c.max_batch || n <= 0 || n > e->ntok_cap) { err = "head_forward: b or n out of range"; return VITX_ERR_INVALID; }
-  e->have_fwd = false;          // the head state of a preceding full forward is overwritten: its backward must not run on it
+  e->have_fwd = false; e->last_cls_only = false;          // the head state of a preceding full forward is overwritten: its backward must not run on it
   const int d = c.dim;
   if (e->params_dirty) engine_refresh_weights(e);
   if (!e->shell_x) DALLOC(e->shell_x, (size_t)e->mp * d * 4, false);
@@ -2279,7 +2458,7 @@ int engine_transformer_forward(vitx_engine* e, const float* tokens_dev, int b, i
   for (int l = 0; l < s0.depth; ++l)
     if ((rc = block_forward(e, s0, 0, l, b, n, 0, nullptr, drop, seed, err)) != VITX_OK) return rc;
   HIPCHK(hipMemcpyAsync(out_dev, s0.ba[s0.depth - 1].x_out, bytes, hipMemcpyDeviceToDevice, e->stream));
-  e->have_fwd = false;   // saved activations no longer describe a full model forward
+  e->have_fwd = false; e->last_cls_only = false;   // saved activations no longer describe a full model forward
   e->have_tf = true; e->tf_b = b; e->tf_n = n; e->tf_drop = drop; e->tf_seed = seed;
   e->last_training = 0;
   return VITX_OK;
@@ -2424,6 +2603,7 @@ int engine_backward(vitx_engine* e, const float* dlogits_dev, float* dimg_dev, s
   }
   dense_wgrad(e, e->yh, d, dlT, e->nc_k, b, e->head);
   const bool mean_pool = !cait && c.pool == VITX_POOL_MEAN;
+  const bool cls_rows = e->last_cls_only;   // the forward ran the last block on the class rows: its output is the compact [b, d] buffer
   const int head_rows = b * head_tok;
   { Prof pr(e, "fill_zero", 0, (double)head_rows * d * 4); launch_fill_zero(e->g, (int64_t)round_up(head_rows, 256) * d * 4, e->stream); }
   {
@@ -2434,12 +2614,12 @@ int engine_backward(vitx_engine* e, const float* dlogits_dev, float* dimg_dev, s
       launch_mean_pool_bwd(e->dpooled, b, head_tok - extra, d, e->g, e->stream, head_tok);
     } else {
       const int64_t ldrow = (int64_t)head_tok * d;
-      launch_layernorm_bwd(e->dyh, T, d, x_last, ldrow, e->mean_h, e->rstd_h, e->params + e->head_g, nullptr, 0, e->g, ldrow, nullptr, 0,
-                           e->red_ws, e->grads + e->head_g, e->grads + e->head_b, nullptr, b, d, e->stream);
+      launch_layernorm_bwd(e->dyh, T, d, cls_rows ? e->cr.x_out : x_last, cls_rows ? (int64_t)d : ldrow, e->mean_h, e->rstd_h, e->params + e->head_g, nullptr, 0,
+                           e->g, ldrow, nullptr, 0, e->red_ws, e->grads + e->head_g, e->grads + e->head_b, nullptr, b, d, e->stream);
     }
     if (extra && d_distill_dev)   // cotangent of the split-off distillation token: the last row of every image
       HIPCHK(hipMemcpy2DAsync(e->g + (int64_t)(ntok - 1) * d, (size_t)ntok * d * 4, d_distill_dev, (size_t)d * 4, (size_t)d * 4, b, hipMemcpyDeviceToDevice, e->stream));
-    if (T) launch_convert(e->g, d, e->g_lp, 1, d, head_rows, d, d, e->stream);
+    if (T && !cls_rows) launch_convert(e->g, d, e->g_lp, 1, d, head_rows, d, d, e->stream);   // (class-row form: the last block makes its own compact copy)
   }
   report_ready(e, e->head_g, e->n_arena - e->head_g);
 
@@ -2474,7 +2654,8 @@ int engine_backward(vitx_engine* e, const float* dlogits_dev, float* dimg_dev, s
     if (merging && l == e->merge_after && (rc = merger_backward(e, s0.ba[l].x_out, b, ntok, err)) != VITX_OK) return rc;
     const int rows_tok = (merging && l > e->merge_after) ? e->merge_t : ntok;
     if (e->layer_kept[0][(size_t)l]) {
-      if ((rc = block_backward(e, s0, 0, l, b, rows_tok, 0, drop, e->last_seed, err, merging ? -1 : next_kept(0, l))) != VITX_OK) return rc;
+      if ((rc = block_backward(e, s0, 0, l, b, rows_tok, 0, drop, e->last_seed, err, merging ? -1 : next_kept(0, l), cls_rows && l == s0.depth - 1)) != VITX_OK)
+        return rc;
     } else {
 #ifndef VITX_COMM_LEGACY_ORDER
       report_ready(e, s0.bp[(size_t)l].p_begin, s0.bp[(size_t)l].p_end - s0.bp[(size_t)l].p_begin);   // dropped layer: final zeros

@@ -24,6 +24,7 @@ const VitxEnvSwitch kSwitches[] = {
     {"VITX_UNFUSED_HEADOPS", VITX_ENV_PATH, "1: head-axis operations (mix / softmax / LayerNorm over heads) as one kernel each"},
     {"VITX_WGRAD_TRANSPOSE", VITX_ENV_PATH, "1: weight gradients through explicit bf16 transposes + the NT kernel"},
     {"VITX_GELU_TABLE", VITX_ENV_PATH, "0: fc1 epilogue evaluates the degree-7 polynomial GELU instead of the LDS table (another rounding of gelu, both inside a bf16 ulp)"},
+    {"VITX_LAST_BLOCK_FULL", VITX_ENV_PATH, "1: the last block of a cls-pooled bf16 ViT on every token row instead of the class rows only (same logits; eight of its parameter gradients sum in another order); read per forward"},
     {"VITX_X3_ATTN", VITX_ENV_PATH, "BF16X3 handles: 1 fused split-operand attention (default), 2 materialised scores + split-operand products, 0 exact fp32 products"},
     {"VITX_F32_MFMA", VITX_ENV_TUNING, "0: parity-mode GEMMs on the scalar-FMA kernel instead of the fp32 matrix pipe (same bits)"},
     // ---- tuning: same results

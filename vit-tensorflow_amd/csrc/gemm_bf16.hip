@@ -445,6 +445,16 @@ static int autotune_enabled() {
   if (on < 0) { const char* v = vitx_env("VITX_GEMM_AUTOTUNE"); on = (v && atoi(v) == 0) ? 0 : 1; }
   return on;
 }
+// The tile variant an automatic (kernel = 0) launch of this shape runs: the measured choice once the shape has been launched in this process, else
+// the static rule (what an untunable shape always takes).  For callers that must reproduce what that launch's epilogue does row by row (the class-row
+// form of the last block: interior tiles of variant 13 round GELU through the table, every other tile through the polynomial).
+int gemm_bf16_variant_for(int mode, int M, int N, int K, int has_scale, int shared_gpu) {
+  const std::array<int64_t, 6> key = {mode, M, N, K, 1, (has_scale != 0) + 2 * (g_shared_gpu | (shared_gpu != 0))};
+  std::lock_guard<std::mutex> lk(g_tune_mu);
+  auto it = g_tuned.find(key);
+  return it != g_tuned.end() ? (it->second & 31) : gemm_bf16_pick(M, N);
+}
+
 void launch_gemm_bf16(const Bf16GemmArgs& g0, const EpiParams& ep, int mode, hipStream_t s) {
   // small batches: a few hundred token rows give the 256x256 tiles less than two per CU, where the smaller tiles can win by a lot
   const bool few_tiles = ceil_div(g0.M, 256) * ceil_div(g0.N, 256) < 512;

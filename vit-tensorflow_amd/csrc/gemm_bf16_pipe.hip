@@ -58,6 +58,11 @@ const uint32_t* gelu_table_dev() {   // one copy per device (one process may dri
   return d;
 }
 
+int gelu_table_on() {
+  static const int on = [] { const char* v = vitx_env("VITX_GELU_TABLE"); return v ? atoi(v) : 1; }();   // 0: the polynomial form everywhere (A/B)
+  return on;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Software-pipelined persistent NT kernel (the default for N >= 256).  Same tile / wave decomposition, LDS image and swizzle as
 // gemm_bf16_nt_kernel, but
@@ -642,8 +647,7 @@ void launch_pipe(const Bf16GemmArgs& g, const EpiParams& ep, hipStream_t s, bool
   // XCD-owned row bands (walk 2): wide outputs on the full persistent grid with enough row tiles for 8-row bands per XCD
   const bool walk2_ok = BM == 256 && zs == 1 && gx == (unsigned)grid_cap && (gx & 7) == 0 && gx < (unsigned)(tiles_m * tiles_n) && tiles_n >= 8 && tiles_m >= 64 && g.stagger != 8;
   gp.walk = (walk2_ok && walk_env != 0) ? 2 : 0;
-  static const int gelu_table_on = [] { const char* v = vitx_env("VITX_GELU_TABLE"); return v ? atoi(v) : 1; }();   // 0: the polynomial form everywhere (A/B)
-  const uint32_t* gtab = (MODE == EPI_BIAS_GELU && BM == 256 && gelu_table_on) ? gelu_table_dev() : nullptr;
+  const uint32_t* gtab = (MODE == EPI_BIAS_GELU && BM == 256 && gelu_table_on()) ? gelu_table_dev() : nullptr;
   hipLaunchKernelGGL(kern, grid, block, SMEM, s, gp, ep, tiles_m, tiles_n, per, gtab);
 }
 
@@ -658,6 +662,9 @@ void pipe_mode(int variant, const Bf16GemmArgs& g, const EpiParams& ep, hipStrea
 }
 
 }  // namespace
+
+// interior 256 x 256 tiles of an EPI_BIAS_GELU launch of variant 13 take GELU from the table, everything else evaluates the polynomial form
+bool gemm_bf16_gelu_table_active() { return gelu_table_on() && gelu_table_dev() != nullptr; }
 
 void launch_gemm_bf16_pipe(int variant, int mode, const Bf16GemmArgs& g, const EpiParams& ep, hipStream_t s) {
   switch (mode) {

@@ -67,6 +67,8 @@ struct Bf16GemmArgs {
                              //   persistent grid, launched on their own behind the full rounds (gemm_bf16.hip: dispatch_gemm_bf16_tail); 0 = one launch
 };
 void launch_gemm_bf16(const Bf16GemmArgs& g, const EpiParams& ep, int mode, hipStream_t s);
+int gemm_bf16_variant_for(int mode, int M, int N, int K, int has_scale, int shared_gpu);   // variant an automatic launch of this shape runs (measured if known, else the static rule)
+bool gemm_bf16_gelu_table_active();   // EPI_BIAS_GELU: interior tiles of variant 13 read GELU from the LDS table (VITX_GELU_TABLE)
 int gemm_bf16_tile_m(int kernel, int M, int N);
 int gemm_bf16_tile_n(int kernel, int M, int N);
 int gemm_bf16_num_slices(int K, int split_k);
@@ -79,14 +81,18 @@ int gemm_bf16_tn_tile(int kernel, int M, int N);
 // ---------------------------------------------------------------- attn_bf16.hip
 // fused multi-head self-attention (vit.py:73-82) on packed qkv [b, n, 3, h, 64] bf16.
 bool attn_bf16_supported(int n, int dim_head);
+// nq_live (both launchers; 0 = n): live-query count.  Forward: only rows < nq_live of o / lse are computed and stored.  Backward: d_o rows >= nq_live
+// are taken as zero (those of a live 16-row query block are read, with their o and lse rows, but cannot reach any stored value: they stay in their own
+// query column, which is stored as zero and gets no D; the others are not read), the dq rows >= nq_live are written as zeros, dk / dv keep the bits of
+// the full launch on such a d_o.
 void launch_attn_bf16_fwd(const bf16_t* qkv, bf16_t* o, float* lse, int b, int n, int h, float scale, const bf16_t* zero_page, int reverse,
-                          hipStream_t s);   // zero_page: >= 128 B of zeros; reverse: 1 = (image, head) tasks from the last to the first
+                          hipStream_t s, int nq_live = 0);   // zero_page: >= 128 B of zeros; reverse: 1 = (image, head) tasks from the last to the first
 // attn_x3.hip: the same fused attention on fp32 storage with split-operand (hi + lo) bf16 MFMA products (BF16X3 mode)
 bool attn_x3_supported(int n, int dim_head);
 void launch_attn_x3_fwd(const float* qkv, float* o, float* lse, int b, int n, int h, float scale, hipStream_t s);
 void launch_attn_x3_bwd(const float* qkv, const float* o, const float* d_o, const float* lse, float* dqkv, int b, int n, int h, float scale, hipStream_t s);
 void launch_attn_bf16_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o, const float* lse, float* dsum_ws,
-                          bf16_t* dqkv, int b, int n, int h, float scale, const bf16_t* zero_page, hipStream_t s);
+                          bf16_t* dqkv, int b, int n, int h, float scale, const bf16_t* zero_page, hipStream_t s, int nq_live = 0);
 
 // ---------------------------------------------------------------- attn_lsa.hip
 // locality self-attention (vit_for_small_dataset.py:88-121) on packed qkv [b, n, 3, h, dh] (fp32 storage: exact fp32 FMA; bf16 storage: every product
@@ -180,6 +186,9 @@ void launch_convert(const float* in, int64_t ldi, void* out, int out_bf16, int64
                     hipStream_t s);
 void launch_to_f32(const void* in, int in_bf16, int64_t ldi, float* out, int64_t ldo, int rows, int cols, hipStream_t s);
 void launch_set_token_row(float* x, const float* tok, int b, int ntok, int row, int d, hipStream_t s);   // x[b, row, :] = tok[:]
+// dst[r][0 : row_bytes) = src[r][0 : row_bytes) for r < rows, rows at independent strides (row_bytes, both strides and both pointers multiples of 16 B):
+// the gather (class row of every image -> compact [b, *]) and the scatter (back) of the last block's class-row form
+void launch_copy_rows(const void* src, int64_t src_stride_bytes, void* dst, int64_t dst_stride_bytes, int rows, int row_bytes, hipStream_t s);
 void launch_mean_pool(const float* x, int b, int ntok, int d, float* out, hipStream_t s, int stride_tok = 0);   // stride_tok: rows per image in memory (0 = ntok)
 void launch_mean_pool_bwd(const float* dp, int b, int ntok, int d, float* g, hipStream_t s, int stride_tok = 0);   // rows >= ntok of an image are left alone
 void launch_batch_reduce(const float* g, int b, int ntok, int d, int j0, int nj, float* out, hipStream_t s);  // out[j][c] = sum_b g[b][j0+j][c]
