@@ -89,7 +89,16 @@ typedef struct vitx_config {
    * VITX_ERR_UNSUPPORTED.  0 (a zeroed struct) = off: the handle is exactly the ordinary one.  Whether the small-head kernels run is the
    * composite's choice per handle (vitx_nest_config.small_attn). */
   int32_t nest_block;
-  int32_t reserved[2];
+  /* twins_svt.GlobalAttention (twins_svt.py:158-190) as the attention of every block: > 0 is the key / value reduction k.  The tokens of a
+   * sequence are the image_h x image_w map (patch_h = patch_w = 1) in row-major order; to_q is a Dense on every token (:167,179), to_kv the
+   * 'valid' Conv2D of kernel and stride k on the normalised map (:168,180), i.e. a Dense [k*k*dim, 2*inner] on the (image_h / k) x (image_w / k)
+   * unfolded windows ((p1 p2 c) feature order = the Keras kernel's), then softmax(q k^T * dim_head^-0.5) v of image_h * image_w queries against
+   * (image_h / k)(image_w / k) keys.  The block's table has attn.to_q.kernel [dim, inner] and attn.to_kv.kernel [k*k*dim, 2*inner] instead of
+   * attn.to_qkv.kernel.  Needs nest_block != 0 (and so everything that flag needs) and image_h, image_w divisible by k; the transformer entry
+   * takes exactly image_h * image_w tokens per sequence.  In the bf16 mode the attention of at most 64 keys at dim_head 64 runs the few-key kernels
+   * (attn_fewkey.hip) unless VITX_GENERIC_ATTN is set or the composite switches them off.  0 (a zeroed struct) = off: the handle is exactly as before. */
+  int32_t global_k;
+  int32_t reserved[1];
 } vitx_config;
 
 typedef struct vitx_engine* vitx_handle;
@@ -540,6 +549,56 @@ int32_t vitx_nest_profile_end(vitx_nest_handle m, vitx_kernel_stat* out, int32_t
 /* "embedded" [b, f, f, dim]; "level.<i>" [b, f_i, f_i, d_i] (the level's output after un-blocking, before aggregation); "aggregated.<i>"
  * [b, f_{i+1}, f_{i+1}, d_{i+1}]; "pooled" [b, d_last] */
 int32_t vitx_nest_read(vitx_nest_handle m, const char* which, float* out_host, int64_t cap_elems, int64_t* n_elems);
+
+/* ---- TwinsSVT (twins_svt.py:215-268): four stages of PatchEmbedding ('b (h p1) (w p2) c -> b h w (c p1 p2)' + 1x1 Conv2D = Dense, :94-106),
+ * Transformer(depth 1), PEG (x + depthwise Conv2D 'SAME' with bias, :108-115), Transformer(depth s_depth) (:252-259); then GlobalAvgPool2D
+ * and Dense (:261-264).  A Transformer layer (:199-213) is local attention on local_patch_size windows (:117-156), MLP (:78-92), global
+ * attention against a global_k-strided reduction of the map (:158-190), MLP, each x + f(LayerNorm_channel(x)) (:37-68); the last stage has
+ * no local pair (has_local=False, :255,258).  Every attention has 8 heads of 64 (:118,159: TwinsSVT passes neither), every MLP mult 4.
+ * The local pairs of a stage run on one vitx_config.nest_block engine over (b * windows) sequences, the global pairs on one
+ * vitx_config.global_k engine over b sequences of the whole map.  A handle of its own; parameter order in DESIGN.md section 21.  Only the
+ * deterministic path (dropout 0) exists. */
+typedef struct vitx_twins_config {
+  /* the map the handle is built for; both 0 is allowed for the host-only table calls (no parameter depends on the image size) */
+  int32_t image_h, image_w;
+  int32_t num_classes;              /* twins_svt.py:217 */
+  int32_t emb_dim[4], patch_size[4], local_patch_size[4], global_k[4], depth[4];   /* s1..s4 (:218-237) */
+  int32_t peg_kernel_size;          /* :238; odd */
+  float ln_eps;                     /* <= 0: twins_svt.py:46's 1e-5 */
+  int32_t compute;                  /* VITX_COMPUTE_*: the transformer blocks' mode; embeddings, PEG and head keep fp32 storage */
+  int32_t max_batch;
+  int32_t device_id;
+  /* the few-key attention kernels of the global pairs (attn_fewkey.hip: bf16 mode, at most 64 keys; K and V staged once in LDS, no score tensor).
+   * 0: where they measured faster than the materialised path at the usage shape -- on.  1: wherever they apply.  -1: nowhere. */
+  int32_t fused_global_attn;
+  int32_t reserved[7];
+} vitx_twins_config;
+typedef struct vitx_twins* vitx_twins_handle;
+/* host only, no GPU needed */
+int32_t vitx_twins_param_table_size(const vitx_twins_config* cfg, int64_t* n_tensors, int64_t* n_elems);
+int32_t vitx_twins_param_table_entry(const vitx_twins_config* cfg, int64_t index, char* name, int32_t name_cap, int64_t shape[4], int32_t* rank,
+                                     int64_t* offset_elems);
+int32_t vitx_twins_create(const vitx_twins_config* cfg, vitx_twins_handle* out);
+int32_t vitx_twins_destroy(vitx_twins_handle m);
+int32_t vitx_twins_set_params(vitx_twins_handle m, const float* host_blob, int64_t n_elems);
+int32_t vitx_twins_get_params(vitx_twins_handle m, float* host_blob, int64_t n_elems);
+int32_t vitx_twins_get_grads(vitx_twins_handle m, float* host_blob, int64_t n_elems);
+int32_t vitx_twins_params_dev(vitx_twins_handle m, float** dev_ptr, int64_t* n_elems);
+int32_t vitx_twins_grads_dev(vitx_twins_handle m, float** dev_ptr, int64_t* n_elems);
+int32_t vitx_twins_params_changed(vitx_twins_handle m);
+/* img [b, image_h, image_w, 3] NHWC; logits [b, num_classes] */
+int32_t vitx_twins_forward(vitx_twins_handle m, const float* img_host, int32_t b, float* logits_host);
+int32_t vitx_twins_forward_dev(vitx_twins_handle m, const float* img_dev, int32_t b, float* logits_dev_or_null);
+/* VJP of the last forward for d(logits): overwrites the gradient arena; d(img) only when asked for */
+int32_t vitx_twins_backward(vitx_twins_handle m, const float* dlogits_host, float* dimg_host_or_null);
+int32_t vitx_twins_backward_dev(vitx_twins_handle m, const float* dlogits_dev, float* dimg_dev_or_null);
+/* per-kernel-class timing of the steps between the two calls, as vitx_profile_begin / _end: every engine's block classes plus the composite's
+ * own (twins_embed, twins_windows, twins_peg_fwd / _bwd, twins_head) */
+int32_t vitx_twins_profile_begin(vitx_twins_handle m);
+int32_t vitx_twins_profile_end(vitx_twins_handle m, vitx_kernel_stat* out, int32_t cap, int32_t* n_out);
+/* "embedded.<s>" (the stage's patch embedding), "pre_peg.<s>", "peg.<s>" (in front of / behind the PEG), "stage.<s>" (the stage's output), each
+ * [b, H_s, W_s, emb_dim_s]; "pooled" [b, emb_dim_4] */
+int32_t vitx_twins_read(vitx_twins_handle m, const char* which, float* out_host, int64_t cap_elems, int64_t* n_elems);
 
 #ifdef __cplusplus
 }

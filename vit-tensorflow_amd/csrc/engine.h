@@ -214,6 +214,7 @@ struct vitx_engine {
   int fwd_np = 0;
   bool last_from_patches = false;
   int tf_b = 0, tf_n = 0;
+  int tf_bwd_low = -1;               // ranged backward: the layer the last backward range began at (the next one must end there)
   float tf_drop = 0.f;               // dropout rate that transformer_forward applied (0 unless training) and the seed of its masks
   uint64_t tf_seed = 0;
   bool have_embed = false, have_head = false;   // efficient.ViT shell: state of the last embed_forward / head_forward
@@ -234,6 +235,7 @@ struct vitx_engine {
   int64_t sc_keep_bytes = 0, sc_keep_budget = 48LL << 30;
   // env switches
   bool force_generic_gemm = false, force_generic_attn = false, wgrad_via_transpose = true;
+  bool fewkey_attn = true;  // global_k handles, bf16 mode: the few-key attention kernels (attn_fewkey.hip) where they apply; twins.hip sets it per handle
   bool small_attn = true;   // nest_block handles: plain small-head attention kernels where they apply; nest.hip sets it per handle (vitx_nest_config.small_attn)
   int gemm_kernel = 0;
   int gemm_tail = 0;      // forced tail variant (VITX_GEMM_TAIL_KERNEL; only with a forced main variant)
@@ -292,8 +294,13 @@ int engine_backward(vitx_engine* e, const float* dlogits_dev, float* dimg_dev, s
 // after a class-row forward: runs the last block again on every row from its saved input (same bits on the class rows) and clears the flag, so that
 // every saved activation of that block exists and a later backward takes the full form (vitx_debug_read)
 int engine_complete_last_block(vitx_engine* e, std::string& err);
-int engine_transformer_forward(vitx_engine* e, const float* tokens_dev, int b, int n, int training, uint64_t seed, float* out_dev, std::string& err);
-int engine_transformer_backward(vitx_engine* e, const float* dout_dev, float* dtokens_dev, std::string& err);
+// l0, l1: the layer range [l0, l1) to run (l1 < 0: the depth).  Contract of a ranged step: the forward ranges may come in any order of calls that
+// respects the data flow; the BACKWARD ranges must be visited top-down, each exactly once per step, starting with the range that ends at the depth --
+// that one zeroes the gradient arena, the others write their blocks' gradients into it.  A backward range that does not end where the previous one of
+// the step began (tf_bwd_low) is refused with VITX_ERR_STATE.
+int engine_transformer_forward(vitx_engine* e, const float* tokens_dev, int b, int n, int training, uint64_t seed, float* out_dev, std::string& err,
+                               int l0 = 0, int l1 = -1);
+int engine_transformer_backward(vitx_engine* e, const float* dout_dev, float* dtokens_dev, std::string& err, int l0 = 0, int l1 = -1);
 int engine_patch_tokens_forward(vitx_engine* e, const float* img_dev, int b, int H, int W, float* tokens_dev, float* patches_f32_dev_or_null,
                                 std::string& err);
 int engine_patch_tokens_backward(vitx_engine* e, const float* dtokens_dev, std::string& err);

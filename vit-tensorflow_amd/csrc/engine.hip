@@ -45,6 +45,11 @@ std::string build_param_table(const vitx_config& c, std::vector<ParamDesc>& out)
   if (nestb && c.num_parallel_branches > 1) return "nest_block does not combine with num_parallel_branches";
   if (nestb && sd) return "nest_block does not combine with small_dataset";
   if (nestb && cctb) return "nest_block does not combine with cct_block";
+  const int64_t gk = c.global_k;   // twins_svt.py:158-190
+  if (gk < 0) return "global_k must be >= 0";
+  if (gk && !nestb) return "global_k needs nest_block";
+  if (gk && (c.patch_h != 1 || c.patch_w != 1)) return "global_k needs patch_h == patch_w == 1 (the tokens are the image_h x image_w map)";
+  if (gk && (c.image_h % gk || c.image_w % gk)) return "global_k must divide image_h and image_w";
   const int64_t pd = (int64_t)c.patch_h * c.patch_w * c.channels * (sd ? 5 : 1);   // SPT: the image and its four shifts (vit_for_small_dataset.py:154)
   int64_t off = 0, aoff = 0;
   auto add = [&](const std::string& n, std::vector<int64_t> s) {
@@ -79,6 +84,9 @@ std::string build_param_table(const vitx_config& c, std::vector<ParamDesc>& out)
       add(pre + ".attn.to_kv.kernel", {d, 2 * inner});
       add(pre + ".attn.mix_heads_pre_attn", {h, h});
       add(pre + ".attn.mix_heads_post_attn", {h, h});
+    } else if (gk) {
+      add(pre + ".attn.to_q.kernel", {d, inner});                   // twins_svt.py:167
+      add(pre + ".attn.to_kv.kernel", {gk * gk * d, 2 * inner});    // :168, the [k, k, d, 2 inner] kernel as rows in (p1 p2 c) order
     } else {
       add(pre + ".attn.to_qkv.kernel", {d, 3 * inner});
     }
@@ -217,6 +225,9 @@ static int dalloc(vitx_engine* e, void** p, size_t bytes, bool t_buffer, std::st
     int rc_ = dalloc(e, (void**)&(ptr), (size_t)(bytes), tb, err);         \
     if (rc_ != VITX_OK) return rc_;                                        \
   } while (0)
+
+// global_k handles: keys per image = windows of the k-strided reduction of the image_h x image_w map (twins_svt.py:168)
+static inline int global_keys(const vitx_config& c) { return (c.image_h / c.global_k) * (c.image_w / c.global_k); }
 
 static int64_t find_param(const vitx_engine* e, const std::string& name) {
   for (auto& p : e->table)
@@ -1000,14 +1011,20 @@ static void attn_generic_bwd(vitx_engine* e, const BlockParams& bp, const AttnVi
 
 // nest_block handles: the plain-softmax form of the small-head kernels (attn_lsa.hip) where the fused kernels above do not apply
 static bool use_small_attn(const vitx_engine* e, int n) {
-  return e->cfg.nest_block && e->small_attn && !e->force_generic_attn && attn_small_supported(n, e->cfg.dim_head);
+  return e->cfg.nest_block && !e->cfg.global_k && e->small_attn && !e->force_generic_attn && attn_small_supported(n, e->cfg.dim_head);
 }
 static bool use_fused_attn(const vitx_engine* e, int n) {
-  return e->bf16 && e->cfg.variant == VITX_VARIANT_VIT && !e->force_generic_attn && attn_bf16_supported(n, e->cfg.dim_head);
+  return e->bf16 && e->cfg.variant == VITX_VARIANT_VIT && !e->cfg.global_k && !e->force_generic_attn && attn_bf16_supported(n, e->cfg.dim_head);
+}
+// global_k handles in the bf16 mode: the few-key kernels (attn_fewkey.hip) for at most 64 keys of dim_head 64
+static bool use_fewkey_attn(const vitx_engine* e, int b, int nq, int nk) {
+  return e->cfg.global_k && e->bf16 && e->fewkey_attn && !e->force_generic_attn && (int64_t)b * e->cfg.heads <= 65535 &&
+         attn_fewkey_supported(nq, nk, e->cfg.dim_head);
 }
 // BF16X3 mode: the fused split-operand attention (attn_x3.hip); VITX_X3_ATTN=2 keeps the materialised path with split-operand products, 0 exact ones
 static bool use_fused_attn_x3(const vitx_engine* e, int n) {
-  return e->x3 && e->x3_attn && e->x3_fused_attn && e->cfg.variant == VITX_VARIANT_VIT && !e->force_generic_attn && attn_x3_supported(n, e->cfg.dim_head);
+  return e->x3 && e->x3_attn && e->x3_fused_attn && e->cfg.variant == VITX_VARIANT_VIT && !e->cfg.global_k && !e->force_generic_attn &&
+         attn_x3_supported(n, e->cfg.dim_head);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1099,7 +1116,7 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
   const vitx_config& c = e->cfg;
   const int d = c.dim, inner = e->inner, m = c.mlp_dim, T = e->bf16, esz = e->esz;
   const int rows = b * nq;
-  const int nk = nq + nc;
+  const int nk = c.global_k ? global_keys(c) : nq + nc;   // (global_k handles: the keys are the reduced map)
   const double lnb = (double)rows * d * (4 + esz);
   if (!ba.skip_attn) {
   {
@@ -1129,6 +1146,18 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
     av.q = ba.q; av.ldq = inner; av.qb = (int64_t)nq * inner;
     av.k = ba.kv; av.ldk = 2 * inner; av.kb = (int64_t)nk * 2 * inner;
     av.v = boff(ba.kv, inner, esz); av.ldv = 2 * inner; av.vb = av.kb;       // cait.py:116
+  } else if (c.global_k) {
+    EpiParams ep; ep.out = ba.q; ep.ldo = inner;
+    dense_fwd(e, ba.y1, d, rows, bp.q, EPI_STORE, ep);                       // twins_svt.py:179
+    {
+      Prof pr(e, "global_kv_unfold", 0, 2.0 * rows * d * esz);
+      launch_twins_kunfold(ba.y1, ba.ctx, T, b, c.image_h, c.image_w, d, c.global_k, bp.kv.in_k, e->stream);
+    }
+    EpiParams ep2; ep2.out = ba.kv; ep2.ldo = 2 * inner;
+    dense_fwd(e, ba.ctx, bp.kv.in_k, b * nk, bp.kv, EPI_STORE, ep2);          // :180, the strided convolution as a Dense on the window rows
+    av.q = ba.q; av.ldq = inner; av.qb = (int64_t)nq * inner;
+    av.k = ba.kv; av.ldk = 2 * inner; av.kb = (int64_t)nk * 2 * inner;
+    av.v = boff(ba.kv, inner, esz); av.ldv = 2 * inner; av.vb = av.kb;       // :181
   } else {
     EpiParams ep; ep.out = ba.qkv; ep.ldo = 3 * inner;
     dense_fwd(e, ba.y1, d, rows, bp.qkv, EPI_STORE, ep);                     // vit.py:72
@@ -1151,10 +1180,14 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
     Prof pr(e, "attn_bf16_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head * live, (double)rows * inner * (2 + 2 * live) * esz);
     launch_attn_bf16_fwd((const bf16_t*)ba.qkv, (bf16_t*)ba.o, ba.lse, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), (const bf16_t*)e->zero_page, (e->reverse_mask >> 2) & 1, e->stream,
                          cls_rows ? 1 : 0);
+  } else if (use_fewkey_attn(e, b, nq, nk)) {   // twins_svt.py:184-187
+    Prof pr(e, "attn_fewkey_fwd", 4.0 * b * c.heads * (double)nq * nk * c.dim_head, ((double)rows * inner * 2 + (double)b * nk * 2 * inner) * esz);
+    launch_attn_fewkey_fwd((const bf16_t*)ba.q, (const bf16_t*)ba.kv, (bf16_t*)ba.o, ba.lse, b, nq, nk, c.heads, inner, 2 * inner, inner,
+                           1.0f / std::sqrt((float)c.dim_head), e->stream);
   } else {
     const int need = c.variant == VITX_VARIANT_VIT ? 1 : 3;
     if (e->keep_scores && ba.sc_keep_elems == 0) {   // first use: this block's own score buffers, sized for the largest call
-      const int64_t emax = (int64_t)c.max_batch * c.heads * st.nq_max * round_up(st.nq_max + st.nc_max, 4);
+      const int64_t emax = (int64_t)c.max_batch * c.heads * st.nq_max * round_up(c.global_k ? global_keys(c) : st.nq_max + st.nc_max, 4);
       if (e->sc_keep_bytes + need * emax * 4 <= e->sc_keep_budget) {
         for (int i = 0; i < need; ++i) DALLOC(ba.sc_keep[i], (size_t)emax * 4, false);
         ba.sc_keep_elems = emax;
@@ -1301,7 +1334,7 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
   BlockActs& ba = st.ba[l];
   const vitx_config& c = e->cfg;
   const int d = c.dim, inner = e->inner, m = c.mlp_dim, T = e->bf16, esz = e->esz;
-  const int rows = b * nq, nk = nq + nc;
+  const int rows = b * nq, nk = c.global_k ? global_keys(c) : nq + nc;
   const void* gT = T ? e->g_lp : (const void*)e->g;   // T view of the residual gradient (re-read after each LayerNorm VJP: side_rotate)
   const double lnb = (double)rows * d * (4 + 4 + 4 + esz + esz);
   // Parallel half-blocks (parallel_vit.py:36-42): every branch of a group sees the SAME output gradient g, and the gradient of the
@@ -1513,6 +1546,36 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
     } else {
       launch_add_T(e->d_y, e->d_ctx, T, (int64_t)rows * d, e->stream);
     }
+  } else if (c.global_k) {
+    av.q = ba.q; av.ldq = inner; av.qb = (int64_t)nq * inner;
+    av.k = ba.kv; av.ldk = 2 * inner; av.kb = (int64_t)nk * 2 * inner;
+    av.v = boff(ba.kv, inner, esz); av.ldv = 2 * inner; av.vb = av.kb;
+    // d_qkv buffer as [dq | dkv], as CaiT's: dq [rows, inner], then dkv [b * nk, 2 * inner]
+    void* dq = e->d_qkv;
+    void* dkv = boff(e->d_qkv, (round_up((int64_t)rows, 256) + 320) * inner, esz);
+    ag.dq = dq; ag.lddq = inner; ag.dqb = (int64_t)nq * inner;
+    ag.dk = dkv; ag.lddk = 2 * inner; ag.dkb = (int64_t)nk * 2 * inner;
+    ag.dv = boff(dkv, inner, esz); ag.lddv = 2 * inner; ag.dvb = ag.dkb;
+    if (use_fewkey_attn(e, b, nq, nk)) {
+      Prof pr(e, "attn_fewkey_bwd", 10.0 * b * c.heads * (double)nq * nk * c.dim_head, ((double)rows * inner * 4 + (double)b * nk * 4 * inner) * esz);
+      launch_attn_fewkey_bwd((const bf16_t*)ba.q, (const bf16_t*)ba.kv, (const bf16_t*)ba.o, (const bf16_t*)d_o, ba.lse, (bf16_t*)dq, (bf16_t*)dkv, b, nq, nk,
+                             c.heads, inner, 2 * inner, inner, inner, inner, 2 * inner, 1.0f / std::sqrt((float)c.dim_head), e->stream);
+    } else {
+      int rc = ensure_scores(e, 4, (int64_t)b * c.heads * nq * round_up(nk, 4), err);
+      if (rc != VITX_OK) return rc;
+      attn_generic_bwd(e, bp, av, ag, b, &ba);
+    }
+    // to_q / to_kv VJPs: d(y1) through q, then the window rows' gradient folded back onto the map and added (twins_svt.py:179-180)
+    EpiParams ep; ep.out = e->d_y; ep.ldo = d;
+    const hipEvent_t fork_qkv = side_prefork(e);                                // dq and dkv are complete
+    dense_dgrad(e, dq, inner, rows, bp.q, EPI_STORE, ep);
+    dense_wgrad(e, ba.y1, d, dq, inner, rows, bp.q, fork_qkv);
+    EpiParams ep2; ep2.out = e->d_ctx; ep2.ldo = bp.kv.in_k;
+    dense_dgrad(e, dkv, 2 * inner, b * nk, bp.kv, EPI_STORE, ep2);
+    dense_wgrad(e, ba.ctx, bp.kv.in_k, dkv, 2 * inner, b * nk, bp.kv, fork_qkv);
+    side_note_read(e, e->rg_dqkv);
+    Prof pr(e, "global_kv_fold", 0, 3.0 * rows * d * esz);
+    launch_twins_kfold_add(e->d_ctx, bp.kv.in_k, e->d_y, T, b, c.image_h, c.image_w, d, c.global_k, e->stream);
   } else {
     av.q = ba.qkv; av.k = boff(ba.qkv, inner, esz); av.v = boff(ba.qkv, 2 * inner, esz);
     av.ldq = av.ldk = av.ldv = 3 * inner;
@@ -1726,6 +1789,9 @@ static int engine_create_body(vitx_engine* e, const vitx_config& cfg, std::strin
         }
         bp.mix_pre = find_param(e, pre + ".attn.mix_heads_pre_attn");
         bp.mix_post = find_param(e, pre + ".attn.mix_heads_post_attn");
+      } else if (c.global_k) {
+        if ((rc = init_dense(e, bp.q, pre + ".attn.to_q.kernel", "", d, inner, err)) != VITX_OK) return rc;
+        if ((rc = init_dense(e, bp.kv, pre + ".attn.to_kv.kernel", "", c.global_k * c.global_k * d, 2 * inner, err)) != VITX_OK) return rc;
       } else {
         if ((rc = init_dense(e, bp.qkv, pre + ".attn.to_qkv.kernel", "", d, 3 * inner, err)) != VITX_OK) return rc;
       }
@@ -1758,6 +1824,12 @@ static int engine_create_body(vitx_engine* e, const vitx_config& cfg, std::strin
         if (nc > 0) DALLOC(ba.ctx, (size_t)crow * d * esz, true);
         DALLOC(ba.fa, (size_t)rows * d * esz, true);
         DALLOC(ba.fm, (size_t)rows * d * esz, true);
+      } else if (c.global_k) {
+        // q of every token; the k-unfolded LayerNorm output (ctx) and kv of the reduced map: (image_h / k)(image_w / k) rows per image
+        const int64_t krow = round_up(B * global_keys(c), 256) + 320;
+        DALLOC(ba.q, (size_t)rows * inner * esz, true);
+        DALLOC(ba.kv, (size_t)krow * 2 * inner * esz, true);
+        DALLOC(ba.ctx, (size_t)krow * bp.kv.in_k * esz, true);
       } else {
         DALLOC(ba.qkv, (size_t)rows * 3 * inner * esz, true);
       }
@@ -1900,7 +1972,10 @@ static int engine_create_body(vitx_engine* e, const vitx_config& cfg, std::strin
   DALLOC(e->d_y, (size_t)rmax * d * esz, true);
   DALLOC(e->d_o, (size_t)rmax * inner * esz, true);
   DALLOC(e->d_qkv, (size_t)(rmax + 256) * 3 * inner * esz + (size_t)crow_max * 2 * inner * esz, true);
-  DALLOC(e->d_ctx, (size_t)crow_max * d * esz, true);
+  // (global_k handles: d(the k-unfolded LayerNorm output), as many rows as an image has keys, k * k * dim features each)
+  const int64_t kfeat = c.global_k ? round_up((int64_t)c.global_k * c.global_k * d, 64) : 0;
+  const int64_t dctx_elems = std::max<int64_t>(crow_max * d, c.global_k ? (round_up(B * global_keys(c), 256) + 320) * kfeat : 0);
+  DALLOC(e->d_ctx, (size_t)dctx_elems * esz, true);
   DALLOC(e->d_br, (size_t)rmax * d * esz, true);
   if (e->side) {
     // ring slots of the buffers the input-gradient chain rewrites while side-stream weight gradients read them (slot 0 = the buffer above)
@@ -1953,9 +2028,9 @@ static int engine_create_body(vitx_engine* e, const vitx_config& cfg, std::strin
   }
   DALLOC(e->zero_page, 256, false);
   DALLOC(e->tmp_f32, (size_t)rmax * std::max<int64_t>(d, e->pd) * 4, false);
-  const int64_t maxfeat = std::max<int64_t>({(int64_t)d, 3LL * inner, (int64_t)m, (int64_t)e->pd_k, (int64_t)e->nc_k});
+  const int64_t maxfeat = std::max<int64_t>({(int64_t)d, 3LL * inner, (int64_t)m, (int64_t)e->pd_k, (int64_t)e->nc_k, kfeat});
   if (e->x3) {   // split-K partials of the weight gradients (dense_wgrad): at most 32 slices of the largest kernel, never more than 256 MB
-    const int64_t max_w = std::max<int64_t>({(int64_t)d * 3 * inner, (int64_t)d * m, (int64_t)e->pd * d, (int64_t)d * c.num_classes, (int64_t)inner * d});
+    const int64_t max_w = std::max<int64_t>({(int64_t)d * 3 * inner, (int64_t)d * m, (int64_t)e->pd * d, (int64_t)d * c.num_classes, (int64_t)inner * d, kfeat * 2 * inner});
     e->partial_elems = std::min<int64_t>(64LL * 1024 * 1024, 32 * max_w);
     DALLOC(e->partial_ws, (size_t)e->partial_elems * 4, false);
   }
@@ -1965,7 +2040,7 @@ static int engine_create_body(vitx_engine* e, const vitx_config& cfg, std::strin
       DALLOC(e->xt, (size_t)e->t_rows * rmax * 2, false);
       DALLOC(e->dyt, (size_t)e->t_rows * rmax * 2, false);
     }
-    const int64_t max_w = std::max<int64_t>({(int64_t)d * 3 * inner, (int64_t)d * m, (int64_t)e->pd * d, (int64_t)d * c.num_classes, (int64_t)inner * d});
+    const int64_t max_w = std::max<int64_t>({(int64_t)d * 3 * inner, (int64_t)d * m, (int64_t)e->pd * d, (int64_t)d * c.num_classes, (int64_t)inner * d, kfeat * 2 * inner});
     e->partial_elems = 512LL * 256 * 256 + 2 * max_w;
     DALLOC(e->partial_ws, (size_t)e->partial_elems * 4, false);
   }
@@ -2442,22 +2517,28 @@ int engine_embed_backward(vitx_engine* e, const float* dtokens_dev, float* dimg_
 // training != 0 with a dropout rate > 0 draws the Dropout masks of vit.py:41,43,64 from (seed, site, element) exactly as the full
 // forward does (the reference calls self.encoder.transformer(tokens, training=training), mae.py:69, simmim.py:116, efficient.py:47);
 // the backward below regenerates the same masks.
-int engine_transformer_forward(vitx_engine* e, const float* tokens_dev, int b, int n, int training, uint64_t seed, float* out_dev, std::string& err) {
+// [l0, l1) (l1 < 0: the depth): the layers to run -- a composite that interleaves the blocks of two handles (twins.hip: local and global pairs) runs
+// each handle's blocks one range at a time; every block keeps its own saved activations (the contract of a ranged step is stated in engine.h)
+int engine_transformer_forward(vitx_engine* e, const float* tokens_dev, int b, int n, int training, uint64_t seed, float* out_dev, std::string& err,
+                               int l0, int l1) {
   const vitx_config& c = e->cfg;
   if (c.variant == VITX_VARIANT_CAIT || c.variant == VITX_VARIANT_PATCH_MERGER) { err = "transformer_forward: ViT / DeepViT only"; return VITX_ERR_UNSUPPORTED; }
   if (c.small_dataset) { err = "transformer_forward: not for small_dataset handles"; return VITX_ERR_UNSUPPORTED; }
   if (b <= 0 || b > c.max_batch || n <= 0 || n > e->ntok_cap) { err = "transformer_forward: b or n out of range"; return VITX_ERR_INVALID; }
+  if (c.global_k && n != c.image_h * c.image_w) { err = "transformer_forward: a global_k handle takes image_h * image_w tokens per sequence"; return VITX_ERR_INVALID; }
+  Stage& s0 = e->stages[0];
+  if (l1 < 0) l1 = s0.depth;
+  if (l0 < 0 || l0 > l1 || l1 > s0.depth) { err = "transformer_forward: layer range out of bounds"; return VITX_ERR_INVALID; }
   ensure_geometry(e, b, n);
   if (e->params_dirty) engine_refresh_weights(e);
-  Stage& s0 = e->stages[0];
   const size_t bytes = (size_t)b * n * c.dim * 4;
-  if (s0.depth == 0) { HIPCHK(hipMemcpyAsync(out_dev, tokens_dev, bytes, hipMemcpyDeviceToDevice, e->stream)); return VITX_OK; }
-  HIPCHK(hipMemcpyAsync(s0.ba[0].x_in, tokens_dev, bytes, hipMemcpyDeviceToDevice, e->stream));
+  if (l0 == l1) { HIPCHK(hipMemcpyAsync(out_dev, tokens_dev, bytes, hipMemcpyDeviceToDevice, e->stream)); return VITX_OK; }
+  HIPCHK(hipMemcpyAsync(s0.ba[(size_t)l0].x_in, tokens_dev, bytes, hipMemcpyDeviceToDevice, e->stream));
   int rc;
   const float drop = training ? c.dropout : 0.f;
-  for (int l = 0; l < s0.depth; ++l)
+  for (int l = l0; l < l1; ++l)
     if ((rc = block_forward(e, s0, 0, l, b, n, 0, nullptr, drop, seed, err)) != VITX_OK) return rc;
-  HIPCHK(hipMemcpyAsync(out_dev, s0.ba[s0.depth - 1].x_out, bytes, hipMemcpyDeviceToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(out_dev, s0.ba[(size_t)l1 - 1].x_out, bytes, hipMemcpyDeviceToDevice, e->stream));
   e->have_fwd = false; e->last_cls_only = false;   // saved activations no longer describe a full model forward
   e->have_tf = true; e->tf_b = b; e->tf_n = n; e->tf_drop = drop; e->tf_seed = seed;
   e->last_training = 0;
@@ -2467,21 +2548,31 @@ int engine_transformer_forward(vitx_engine* e, const float* tokens_dev, int b, i
 // VJP of engine_transformer_forward: d(out) [b,n,dim] -> d(tokens) [b,n,dim] and the gradients of the transformer's parameters
 // (every other entry of the gradient arena is zero).  This is what lets the wrappers that call encoder.transformer(tokens)
 // on a subset of the patches (mae.py:69, simmim.py:116) train the encoder.
-int engine_transformer_backward(vitx_engine* e, const float* dout_dev, float* dtokens_dev, std::string& err) {
+// [l0, l1): the range of a ranged forward; the gradient arena is zeroed by the range that ends at the depth (the first one a backward pass
+// reaches) and keeps the other ranges' gradients otherwise
+int engine_transformer_backward(vitx_engine* e, const float* dout_dev, float* dtokens_dev, std::string& err, int l0, int l1) {
   const vitx_config& c = e->cfg;
   if (!e->have_tf) { err = "transformer_backward requires a preceding transformer_forward"; return VITX_ERR_STATE; }
   const int b = e->tf_b, n = e->tf_n, d = c.dim, T = e->bf16;
   Stage& s0 = e->stages[0];
   const size_t bytes = (size_t)b * n * d * 4;
-  { Prof pr(e, "fill_zero", 0, (double)e->n_arena * 4); launch_fill_zero(e->grads, (int64_t)e->n_arena * 4, e->stream); }
+  if (l1 < 0) l1 = s0.depth;
+  if (l0 < 0 || l0 > l1 || l1 > s0.depth) { err = "transformer_backward: layer range out of bounds"; return VITX_ERR_INVALID; }
+  if (l1 != s0.depth && l1 != e->tf_bwd_low) { err = "transformer_backward: layer ranges of a step go top-down, each once, from the range that ends at the depth"; return VITX_ERR_STATE; }
+  e->tf_bwd_low = l0;
+  if (l1 == s0.depth) { Prof pr(e, "fill_zero", 0, (double)e->n_arena * 4); launch_fill_zero(e->grads, (int64_t)e->n_arena * 4, e->stream); }
+  if (l0 == l1) {
+    if (dtokens_dev && dtokens_dev != dout_dev) HIPCHK(hipMemcpyAsync(dtokens_dev, dout_dev, bytes, hipMemcpyDeviceToDevice, e->stream));
+    return VITX_OK;
+  }
   launch_fill_zero(e->g, (int64_t)round_up((int64_t)b * n, 256) * d * 4, e->stream);
   HIPCHK(hipMemcpyAsync(e->g, dout_dev, bytes, hipMemcpyDeviceToDevice, e->stream));
   if (T) launch_convert(e->g, d, e->g_lp, 1, d, b * n, d, d, e->stream);
   int rc;
   SideScope side_scope(e, true);
   e->dbr_ready = 0;
-  for (int l = s0.depth - 1; l >= 0; --l)
-    if ((rc = block_backward(e, s0, 0, l, b, n, 0, e->tf_drop, e->tf_seed, err, l - 1)) != VITX_OK) return rc;
+  for (int l = l1 - 1; l >= l0; --l)
+    if ((rc = block_backward(e, s0, 0, l, b, n, 0, e->tf_drop, e->tf_seed, err, l > l0 ? l - 1 : -1)) != VITX_OK) return rc;
   if (dtokens_dev) HIPCHK(hipMemcpyAsync(dtokens_dev, e->g, bytes, hipMemcpyDeviceToDevice, e->stream));
   return VITX_OK;
 }

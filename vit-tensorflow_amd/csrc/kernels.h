@@ -136,15 +136,43 @@ void launch_cct_relu_maxpool_bwd(const float* conv, const float* dout, float* dc
 // ---------------------------------------------------------------- nest_ops.hip
 // NesT (nest.py:137-148,207-212): block partition fused with the positional add, its inverse, their VJPs, and the plain 'SAME' max-pool
 // tokens[(b b1 b2), (h w), c] = x[b, (b1 h), (b2 w), c] + pos[h * w_ + w]   (x: [b, nb * hb, nb * wb, c]; pos == nullptr: the pure copy)
-void launch_nest_to_blocks(const float* x, const float* pos, float* tokens, int b, int nb, int hb, int wb, int c, hipStream_t s);
+// nbx > 0: a rectangular grid of nb x nbx blocks (twins_svt.py:141,153: '(b x y) p1 p2 c' windows of a rectangular map); 0: nb x nb
+void launch_nest_to_blocks(const float* x, const float* pos, float* tokens, int b, int nb, int hb, int wb, int c, hipStream_t s, int nbx = 0);
 // x[b, (b1 h), (b2 w), c] = tokens[(b b1 b2), (h w), c]
-void launch_nest_from_blocks(const float* tokens, float* x, int b, int nb, int hb, int wb, int c, hipStream_t s);
+void launch_nest_from_blocks(const float* tokens, float* x, int b, int nb, int hb, int wb, int c, hipStream_t s, int nbx = 0);
 // d(pos)[j] = sum over sequences and channels of dtokens[seq, j, :]: one partial row per sequence (part: [nseq, n]), then launch_sum_rows
 void launch_nest_dpos(const float* dtokens, float* part, float* dpos, int nseq, int n, int c, hipStream_t s);
 // MaxPool2D(padding='SAME') on a signed input (the running maximum starts at -inf; taps outside the map never win) and its gather-form VJP
 // (every element of dx written; the first maximum in row-major window order takes the window's gradient; no atomics)
 void launch_nest_maxpool_fwd(const float* x, float* out, int b, int H, int W, int C, int k, int st, hipStream_t s);
 void launch_nest_maxpool_bwd(const float* x, const float* dout, float* dx, int b, int H, int W, int C, int k, int st, hipStream_t s);
+
+// ---------------------------------------------------------------- attn_fewkey.hip
+// softmax(q k^T scale) v of nq queries against nk <= 64 keys per (image, head), dim_head 64, bf16 storage, MFMA products, no score tensor:
+// q [b, nq, ldq], kv [b, nk, ldkv] = [k | v] (v at column heads * 64), o [b, nq, ldo], lse [b, heads, nq]; the VJP writes dq [b, nq, lddq] and
+// dkv [b, nk, lddkv] = [dk | dv] (one workgroup per (image, head): no second pass)
+bool attn_fewkey_supported(int nq, int nk, int dim_head);
+void launch_attn_fewkey_fwd(const bf16_t* q, const bf16_t* kv, bf16_t* o, float* lse, int b, int nq, int nk, int heads, int64_t ldq, int64_t ldkv,
+                            int64_t ldo, float scale, hipStream_t s);
+void launch_attn_fewkey_bwd(const bf16_t* q, const bf16_t* kv, const bf16_t* o, const bf16_t* d_o, const float* lse, bf16_t* dq, bf16_t* dkv, int b, int nq,
+                            int nk, int heads, int64_t ldq, int64_t ldkv, int64_t ldo, int64_t lddo, int64_t lddq, int64_t lddkv, float scale, hipStream_t s);
+
+// ---------------------------------------------------------------- twins_ops.hip
+// TwinsSVT PatchEmbedding's Rearrange (twins_svt.py:103): out[(b h w), (c p1 p2)] = x[b, h p + p1, w p + p2, c] (row stride ld), and its VJP,
+// the inverse permutation (every element of dx written)
+void launch_twins_patch_gather(const float* x, float* out, int b, int H, int W, int C, int p, int64_t ld, hipStream_t s);
+void launch_twins_patch_scatter(const float* dpatches, int64_t ld, float* dx, int b, int H, int W, int C, int p, hipStream_t s);
+// rows of the non-overlapping k x k windows of x [b, H, W, C] in (p1 p2 c) order, one row per window (row stride ldo >= k k C), on fp32 or
+// bf16 storage; the VJP ADDS d(windows) into dx [b, H, W, C].  H and W are multiples of k.
+void launch_twins_kunfold(const void* x, void* out, int is_bf16, int b, int H, int W, int C, int k, int64_t ldo, hipStream_t s);
+void launch_twins_kfold_add(const void* dwin, int64_t ld, void* dx, int is_bf16, int b, int H, int W, int C, int k, hipStream_t s);
+// PEG (twins_svt.py:108-115): out = x + bias + depthwise 'SAME' convolution of x with kern [kp, kp, 1, C] (kp odd), NHWC fp32; its VJPs:
+// dx = dy + correlation of dy with the flipped kernel; dkern [kp, kp, 1, C] as partials over fixed pixel slices (ws: twins_peg_ws_elems
+// floats) summed in order.  d(bias) is launch_colsum of dy.
+void launch_twins_peg_fwd(const float* x, const float* kern, const float* bias, float* out, int b, int H, int W, int C, int kp, hipStream_t s);
+void launch_twins_peg_bwd_dx(const float* dy, const float* kern, float* dx, int b, int H, int W, int C, int kp, hipStream_t s);
+int64_t twins_peg_ws_elems(int C, int kp);
+void launch_twins_peg_bwd_dkern(const float* x, const float* dy, float* ws, float* dkern, int b, int H, int W, int C, int kp, hipStream_t s);
 
 // ---------------------------------------------------------------- elementwise.hip
 void launch_unfold(const float* img, void* out, int out_bf16, int b, int H, int W, int C, int ph, int pw,

@@ -26,11 +26,12 @@ bool vec4_ok(int C, const void* a, const void* b, const void* c) {
   return C % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
 }
 
-// One thread per V channels of one token.  e walks the TOKEN layout [(b b1 b2), (h w), c]; the map element is x[b, b1 * hb + h, b2 * wb + w, c].
+// One thread per V channels of one token.  e walks the TOKEN layout [(b b1 b2), (h w), c]; the map element is x[b, b1 * hb + h, b2 * wb + w, c];
+// the grid has nb x nbx blocks.
 // TO_BLOCKS: tokens[e] = x[...] (+ pos[h * wb + w]); else x[...] = tokens[e].
 template <int V, bool TO_BLOCKS>
 __global__ __launch_bounds__(256) void nest_blocks_kernel(const float* __restrict__ src, const float* __restrict__ pos, float* __restrict__ dst, int64_t total,
-                                                          int nb, int hb, int wb, int CV) {
+                                                          int nb, int nbx, int hb, int wb, int CV) {
   using T = typename VecT<V>::type;
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total) return;
@@ -38,10 +39,10 @@ __global__ __launch_bounds__(256) void nest_blocks_kernel(const float* __restric
   int64_t r = e / CV;
   const int w = (int)(r % wb); r /= wb;
   const int h = (int)(r % hb); r /= hb;
-  const int b2 = (int)(r % nb); r /= nb;
+  const int b2 = (int)(r % nbx); r /= nbx;
   const int b1 = (int)(r % nb);
   const int64_t bi = r / nb;
-  const int64_t m = (((bi * nb + b1) * hb + h) * ((int64_t)nb * wb) + (int64_t)b2 * wb + w) * CV + cv;
+  const int64_t m = (((bi * nb + b1) * hb + h) * ((int64_t)nbx * wb) + (int64_t)b2 * wb + w) * CV + cv;
   if (TO_BLOCKS) {
     T v = reinterpret_cast<const T*>(src)[m];
     if (pos != nullptr) {
@@ -144,23 +145,25 @@ __global__ __launch_bounds__(256) void nest_maxpool_bwd_kernel(const float* __re
 
 }  // namespace
 
-void launch_nest_to_blocks(const float* x, const float* pos, float* tokens, int b, int nb, int hb, int wb, int c, hipStream_t s) {
+void launch_nest_to_blocks(const float* x, const float* pos, float* tokens, int b, int nb, int hb, int wb, int c, hipStream_t s, int nbx) {
+  if (nbx <= 0) nbx = nb;
   if (vec4_ok(c, x, tokens, nullptr)) {
-    const int64_t total = (int64_t)b * nb * nb * hb * wb * (c / 4);
-    if (total) hipLaunchKernelGGL((nest_blocks_kernel<4, true>), dim3(grid256(total)), dim3(256), 0, s, x, pos, tokens, total, nb, hb, wb, c / 4);
+    const int64_t total = (int64_t)b * nb * nbx * hb * wb * (c / 4);
+    if (total) hipLaunchKernelGGL((nest_blocks_kernel<4, true>), dim3(grid256(total)), dim3(256), 0, s, x, pos, tokens, total, nb, nbx, hb, wb, c / 4);
   } else {
-    const int64_t total = (int64_t)b * nb * nb * hb * wb * c;
-    if (total) hipLaunchKernelGGL((nest_blocks_kernel<1, true>), dim3(grid256(total)), dim3(256), 0, s, x, pos, tokens, total, nb, hb, wb, c);
+    const int64_t total = (int64_t)b * nb * nbx * hb * wb * c;
+    if (total) hipLaunchKernelGGL((nest_blocks_kernel<1, true>), dim3(grid256(total)), dim3(256), 0, s, x, pos, tokens, total, nb, nbx, hb, wb, c);
   }
 }
 
-void launch_nest_from_blocks(const float* tokens, float* x, int b, int nb, int hb, int wb, int c, hipStream_t s) {
+void launch_nest_from_blocks(const float* tokens, float* x, int b, int nb, int hb, int wb, int c, hipStream_t s, int nbx) {
+  if (nbx <= 0) nbx = nb;
   if (vec4_ok(c, x, tokens, nullptr)) {
-    const int64_t total = (int64_t)b * nb * nb * hb * wb * (c / 4);
-    if (total) hipLaunchKernelGGL((nest_blocks_kernel<4, false>), dim3(grid256(total)), dim3(256), 0, s, tokens, (const float*)nullptr, x, total, nb, hb, wb, c / 4);
+    const int64_t total = (int64_t)b * nb * nbx * hb * wb * (c / 4);
+    if (total) hipLaunchKernelGGL((nest_blocks_kernel<4, false>), dim3(grid256(total)), dim3(256), 0, s, tokens, (const float*)nullptr, x, total, nb, nbx, hb, wb, c / 4);
   } else {
-    const int64_t total = (int64_t)b * nb * nb * hb * wb * c;
-    if (total) hipLaunchKernelGGL((nest_blocks_kernel<1, false>), dim3(grid256(total)), dim3(256), 0, s, tokens, (const float*)nullptr, x, total, nb, hb, wb, c);
+    const int64_t total = (int64_t)b * nb * nbx * hb * wb * c;
+    if (total) hipLaunchKernelGGL((nest_blocks_kernel<1, false>), dim3(grid256(total)), dim3(256), 0, s, tokens, (const float*)nullptr, x, total, nb, nbx, hb, wb, c);
   }
 }
 

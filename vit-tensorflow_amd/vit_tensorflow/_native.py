@@ -24,13 +24,13 @@ class VitxError(RuntimeError):
 
 
 class _ConfigFlags(C.Structure):
-    _fields_ = [("cct_block", C.c_int32), ("nest_block", C.c_int32)]
+    _fields_ = [("cct_block", C.c_int32), ("nest_block", C.c_int32), ("global_k", C.c_int32)]
 
 
 class _ConfigTail(C.Union):
-    """The last four words of vitx_config.  include/vitx.h carved cct_block and nest_block out of the first two reserved words; `reserved` keeps
-    its four-word view here (reserved[0] is cct_block, reserved[1] nest_block), so code that zeroes or inspects it by that name sees the layout
-    it always saw."""
+    """The last four words of vitx_config.  include/vitx.h carved cct_block, nest_block and global_k out of the first three reserved words;
+    `reserved` keeps its four-word view here (reserved[0] is cct_block, reserved[1] nest_block, reserved[2] global_k), so code that zeroes or
+    inspects it by that name sees the layout it always saw."""
     _anonymous_ = ("_flags",)
     _fields_ = [("reserved", C.c_int32 * 4), ("_flags", _ConfigFlags)]
 
@@ -102,6 +102,16 @@ class NesTConfig(C.Structure):
         ("num_hierarchies", C.c_int32), ("block_repeats", C.c_int32 * 8), ("mlp_mult", C.c_int32),
         ("ln_eps", C.c_float), ("compute", C.c_int32), ("max_batch", C.c_int32), ("device_id", C.c_int32), ("conv_chunk", C.c_int32),
         ("small_attn", C.c_int32), ("reserved", C.c_int32 * 7),
+    ]
+
+
+class TwinsConfig(C.Structure):
+    _fields_ = [
+        ("image_h", C.c_int32), ("image_w", C.c_int32), ("num_classes", C.c_int32),
+        ("emb_dim", C.c_int32 * 4), ("patch_size", C.c_int32 * 4), ("local_patch_size", C.c_int32 * 4), ("global_k", C.c_int32 * 4),
+        ("depth", C.c_int32 * 4), ("peg_kernel_size", C.c_int32),
+        ("ln_eps", C.c_float), ("compute", C.c_int32), ("max_batch", C.c_int32), ("device_id", C.c_int32),
+        ("fused_global_attn", C.c_int32), ("reserved", C.c_int32 * 7),
     ]
 
 
@@ -271,6 +281,23 @@ SYMBOLS: List[Tuple[str, object, list]] = [
     ("vitx_nest_profile_begin", C.c_int32, [C.c_void_p]),
     ("vitx_nest_profile_end", C.c_int32, [C.c_void_p, _P(KernelStat), C.c_int32, _P(C.c_int32)]),
     ("vitx_nest_read", C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, _P(C.c_int64)]),
+    ("vitx_twins_param_table_size", C.c_int32, [_P(TwinsConfig), _P(C.c_int64), _P(C.c_int64)]),
+    ("vitx_twins_param_table_entry", C.c_int32, [_P(TwinsConfig), C.c_int64, C.c_char_p, C.c_int32, _P(C.c_int64), _P(C.c_int32), _P(C.c_int64)]),
+    ("vitx_twins_create", C.c_int32, [_P(TwinsConfig), _P(C.c_void_p)]),
+    ("vitx_twins_destroy", C.c_int32, [C.c_void_p]),
+    ("vitx_twins_set_params", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_twins_get_params", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_twins_get_grads", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_twins_params_dev", C.c_int32, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)]),
+    ("vitx_twins_grads_dev", C.c_int32, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)]),
+    ("vitx_twins_params_changed", C.c_int32, [C.c_void_p]),
+    ("vitx_twins_forward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("vitx_twins_forward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("vitx_twins_backward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("vitx_twins_backward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("vitx_twins_profile_begin", C.c_int32, [C.c_void_p]),
+    ("vitx_twins_profile_end", C.c_int32, [C.c_void_p, _P(KernelStat), C.c_int32, _P(C.c_int32)]),
+    ("vitx_twins_read", C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, _P(C.c_int64)]),
 ]
 
 _lib = None
@@ -332,6 +359,11 @@ def cct_param_table(cfg: CCTConfig):
 def nest_param_table(cfg: NesTConfig):
     """[(name, shape, offset)] of NesT's variables from the C library (host-only call; no GPU needed)."""
     return table_of("vitx_nest", C.byref(cfg))
+
+
+def twins_param_table(cfg: TwinsConfig):
+    """[(name, shape, offset)] of TwinsSVT's variables from the C library (host-only call; no GPU needed)."""
+    return table_of("vitx_twins", C.byref(cfg))
 
 
 def mim_param_table(handle, prefix="vitx_mim"):
