@@ -98,7 +98,18 @@ typedef struct vitx_config {
    * takes exactly image_h * image_w tokens per sequence.  In the bf16 mode the attention of at most 64 keys at dim_head 64 runs the few-key kernels
    * (attn_fewkey.hip) unless VITX_GENERIC_ATTN is set or the composite switches them off.  0 (a zeroed struct) = off: the handle is exactly as before. */
   int32_t global_k;
-  int32_t reserved[1];
+  /* cvt.Attention (cvt.py:94-127) as the attention of every block -- the last spare word of the struct, as two halves: conv_proj_kernel > 0 is
+   * proj_kernel, conv_proj_stride kv_proj_stride (>= 1).  The tokens of a sequence are the image_h x image_w map (patch_h = patch_w = 1) in
+   * row-major order.  to_q and to_kv are DepthWiseConv2d (:79-92): a depthwise 'SAME' convolution without bias (stride 1 for q,
+   * conv_proj_stride for kv: ceil(image_h / s) x ceil(image_w / s) keys, TensorFlow's uneven padding), BatchNormalization (eps bn_eps of the
+   * composite, 1e-5) over every position of the call's batch, and a pointwise Dense without bias (csrc/cvt_ops.hip).  The block's table has
+   * attn.to_q.dw.kernel [k, k, 1, dim], attn.to_q.bn.gamma / .beta / .moving_mean / .moving_variance [dim], attn.to_q.pw.kernel [dim, inner]
+   * and the same under attn.to_kv (pw.kernel [dim, 2 * inner]) instead of attn.to_qkv.kernel.  Needs nest_block != 0 and global_k == 0; the
+   * transformer entry takes exactly image_h * image_w tokens per sequence.  In the bf16 mode the attention of at most 64 keys at dim_head 64
+   * runs the few-key kernels unless VITX_GENERIC_ATTN is set or the composite switches them off.  The moving statistics are read only by
+   * forwards the composite marks as inference (vitx_cvt_forward, training == 0); no forward updates them and their gradients are zeros.
+   * 0 (a zeroed struct) = off: the handle is exactly as before.  The struct has no spare word left. */
+  int16_t conv_proj_kernel, conv_proj_stride;
 } vitx_config;
 
 typedef struct vitx_engine* vitx_handle;
@@ -599,6 +610,62 @@ int32_t vitx_twins_profile_end(vitx_twins_handle m, vitx_kernel_stat* out, int32
 /* "embedded.<s>" (the stage's patch embedding), "pre_peg.<s>", "peg.<s>" (in front of / behind the PEG), "stage.<s>" (the stage's output), each
  * [b, H_s, W_s, emb_dim_s]; "pooled" [b, emb_dim_4] */
 int32_t vitx_twins_read(vitx_twins_handle m, const char* which, float* out_host, int64_t cap_elems, int64_t* n_elems);
+
+/* ---- CvT (cvt.py:149-202): three stages of Conv2D(emb_dim, emb_kernel, 'SAME', emb_stride) with bias (:187, im2col + GEMM), channel LayerNorm
+ * (:30-43,188) and a Transformer (:129-147,189-191) of `depth` layers x + Attention(LayerNorm x), x + MLP(LayerNorm x); then GlobalAvgPool2D and
+ * Dense (:195-198).  Attention (:94-127) projects q and kv through DepthWiseConv2d (:79-92) -- depthwise 'SAME' convolution of proj_kernel
+ * (stride 1 for q, kv_proj_stride for kv), BatchNormalization (:85), pointwise Dense -- and attends heads of 64 (:130: CvT never passes
+ * dim_head); to_out always projects (:106-109).  MLP (:63-77) is two 1x1 convolutions around the exact GELU (:23-28).  A stage's blocks run
+ * on one vitx_config.conv_proj_kernel engine over b sequences of the whole map.  A handle of its own; parameter order in DESIGN.md section 22.
+ * Only the deterministic path (dropout 0) exists.  BatchNormalization: a training forward normalises with the statistics of the call's whole
+ * batch and has a VJP; an inference forward normalises with moving_mean / moving_variance of the table and has none (vitx_cvt_backward
+ * returns VITX_ERR_UNSUPPORTED after it).  No forward updates the moving statistics; their gradients are zeros. */
+typedef struct vitx_cvt_config {
+  /* the image the handle is built for; both 0 is allowed for the host-only table calls (no parameter depends on the image size) */
+  int32_t image_h, image_w;
+  int32_t num_classes;              /* cvt.py:151 */
+  /* s1..s3 (:152-175) */
+  int32_t emb_dim[3], emb_kernel[3], emb_stride[3], proj_kernel[3], kv_proj_stride[3], heads[3], depth[3], mlp_mult[3];
+  float ln_eps;                     /* <= 0: cvt.py:31's 1e-5 */
+  float bn_eps;                     /* <= 0: cvt.py:85's 1e-5 */
+  int32_t compute;                  /* VITX_COMPUTE_*: the transformer blocks' mode; embeddings and head keep fp32 storage */
+  int32_t max_batch;
+  int32_t device_id;
+  /* the fused attention kernels of attn_fewkey.hip (bf16 mode, heads of 64; K and V of an (image, head) staged once in LDS, no score tensor): the
+   * few-key ones for at most 64 keys and the many-key ones (key chunks of 64 with an online softmax; d(k) / d(v) per chunk and d(q) as two
+   * launches) for 65 .. 320 keys.  0: per class, where they measured faster than the materialised path at the usage shape (DESIGN.md
+   * section 22).  1: wherever they apply.  -1: nowhere.  More keys, and the fp32 / bf16x3 modes, take the materialised path. */
+  int32_t fused_attn;
+  int32_t reserved[8];
+} vitx_cvt_config;
+typedef struct vitx_cvt* vitx_cvt_handle;
+/* host only, no GPU needed */
+int32_t vitx_cvt_param_table_size(const vitx_cvt_config* cfg, int64_t* n_tensors, int64_t* n_elems);
+int32_t vitx_cvt_param_table_entry(const vitx_cvt_config* cfg, int64_t index, char* name, int32_t name_cap, int64_t shape[4], int32_t* rank,
+                                   int64_t* offset_elems);
+int32_t vitx_cvt_create(const vitx_cvt_config* cfg, vitx_cvt_handle* out);
+int32_t vitx_cvt_destroy(vitx_cvt_handle m);
+int32_t vitx_cvt_set_params(vitx_cvt_handle m, const float* host_blob, int64_t n_elems);
+int32_t vitx_cvt_get_params(vitx_cvt_handle m, float* host_blob, int64_t n_elems);
+int32_t vitx_cvt_get_grads(vitx_cvt_handle m, float* host_blob, int64_t n_elems);
+int32_t vitx_cvt_params_dev(vitx_cvt_handle m, float** dev_ptr, int64_t* n_elems);
+int32_t vitx_cvt_grads_dev(vitx_cvt_handle m, float** dev_ptr, int64_t* n_elems);
+int32_t vitx_cvt_params_changed(vitx_cvt_handle m);
+/* CvT.call(img, training) (cvt.py:200-202).  img [b, image_h, image_w, 3] NHWC; logits [b, num_classes]; training != 0: BatchNormalization on
+ * the statistics of these b images (the reference's default), 0: on the moving statistics */
+int32_t vitx_cvt_forward(vitx_cvt_handle m, const float* img_host, int32_t b, int32_t training, float* logits_host);
+int32_t vitx_cvt_forward_dev(vitx_cvt_handle m, const float* img_dev, int32_t b, int32_t training, float* logits_dev_or_null);
+/* VJP of the last training forward for d(logits): overwrites the gradient arena; d(img) only when asked for */
+int32_t vitx_cvt_backward(vitx_cvt_handle m, const float* dlogits_host, float* dimg_host_or_null);
+int32_t vitx_cvt_backward_dev(vitx_cvt_handle m, const float* dlogits_dev, float* dimg_dev_or_null);
+/* per-kernel-class timing of the steps between the two calls, as vitx_profile_begin / _end: every engine's block classes (cvt_dwbn_fwd / _bwd
+ * among them) plus the composite's own (cvt_im2col, cvt_conv_gemm, cvt_col2im, cvt_embed_norm, cvt_head) */
+int32_t vitx_cvt_profile_begin(vitx_cvt_handle m);
+int32_t vitx_cvt_profile_end(vitx_cvt_handle m, vitx_kernel_stat* out, int32_t cap, int32_t* n_out);
+/* "embedded.<s>" (the stage's embedding behind its LayerNorm) and "stage.<s>" (its output), each [b, H_s, W_s, emb_dim_s]; "q_in.<s>.<l>"
+ * [b, H_s, W_s, emb_dim_s] and "kv_in.<s>.<l>" [b, ceil(H_s / stride), ceil(W_s / stride), emb_dim_s] (the inputs of layer l's pointwise
+ * projections, behind BatchNormalization, widened to fp32); "pooled" [b, emb_dim_3] */
+int32_t vitx_cvt_read(vitx_cvt_handle m, const char* which, float* out_host, int64_t cap_elems, int64_t* n_elems);
 
 #ifdef __cplusplus
 }

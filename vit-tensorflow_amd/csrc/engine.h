@@ -56,8 +56,12 @@ struct Dense {
   float *ext_gw = nullptr, *ext_gb = nullptr;
 };
 
+// conv_proj handles: arena offsets of one DepthWiseConv2d in front of its pointwise Dense (cvt.py:84-85)
+struct ConvProj { int64_t dw = -1, gamma = -1, beta = -1, mmean = -1, mvar = -1; };
+
 struct BlockParams {
   int64_t a_scale = -1, ln1_g = -1, ln1_b = -1;
+  ConvProj cq, ckv;
   int64_t temp = -1;               // LSA temperature (small_dataset handles)
   Dense qkv, q, kv, out;
   Dense qkvcat;   // CaiT patch stage, bf16 mode: operand copies of [to_q | to_kv] side by side (w = -1: no parameter of its own)
@@ -73,6 +77,10 @@ struct BlockActs {
   void *y1 = nullptr, *qkv = nullptr, *q = nullptr, *kv = nullptr, *ctx = nullptr, *o = nullptr, *fa = nullptr;
   void *y2 = nullptr, *hpre = nullptr, *act = nullptr, *fm = nullptr;
   float *mean1 = nullptr, *rstd1 = nullptr, *mean2 = nullptr, *rstd2 = nullptr, *lse = nullptr;
+  // conv_proj handles: the q projection's Dense input (the kv one's is ctx), the fp32 depthwise-convolution outputs and their (mean | rstd) in double
+  void* qin = nullptr;
+  float *cq = nullptr, *ckv = nullptr;
+  double *stq = nullptr, *stkv = nullptr;
   // parallel branches (parallel_vit.py:36-42): a layer of P attention + P feed-forward blocks is laid out as 2P half-blocks.  Each
   // adds its branch to the running residual (x_in -> x_mid, or x_mid -> x_out) but normalises the LAYER's input (ln*_src) --
   // null = the residual input itself, i.e. the ordinary block.
@@ -194,6 +202,10 @@ struct vitx_engine {
   float* red_ws = nullptr; int64_t red_elems = 0;
   float* sc[4] = {nullptr, nullptr, nullptr, nullptr}; int64_t sc_elems = 0;
   float* dsum = nullptr;
+  // conv_proj handles: fp32 d(convolution output) of the q / kv projection, slice partials; cvt.hip sets bn_eps and, per forward, bn_inference
+  float *cv_dq = nullptr, *cv_dkv = nullptr, *cv_ws = nullptr;
+  float bn_eps = 1e-5f;
+  bool bn_inference = false;         // BatchNormalization on the moving statistics of the table (forward only)
   void* zero_page = nullptr;         // 256 B of zeros (source of the padded rows in the attention DMA staging)
   float* tmp_f32 = nullptr;          // [mp, max(d, pd)] fp32 scratch (dropout / dimg paths)
   float* loss_rows = nullptr;
@@ -236,6 +248,7 @@ struct vitx_engine {
   // env switches
   bool force_generic_gemm = false, force_generic_attn = false, wgrad_via_transpose = true;
   bool fewkey_attn = true;  // global_k handles, bf16 mode: the few-key attention kernels (attn_fewkey.hip) where they apply; twins.hip sets it per handle
+  bool manykey_attn = true; // conv_proj handles, bf16 mode: the many-key attention kernels (64 < keys <= MANYKEY_MAX); cvt.hip sets it per handle
   bool small_attn = true;   // nest_block handles: plain small-head attention kernels where they apply; nest.hip sets it per handle (vitx_nest_config.small_attn)
   int gemm_kernel = 0;
   int gemm_tail = 0;      // forced tail variant (VITX_GEMM_TAIL_KERNEL; only with a forced main variant)

@@ -50,6 +50,11 @@ std::string build_param_table(const vitx_config& c, std::vector<ParamDesc>& out)
   if (gk && !nestb) return "global_k needs nest_block";
   if (gk && (c.patch_h != 1 || c.patch_w != 1)) return "global_k needs patch_h == patch_w == 1 (the tokens are the image_h x image_w map)";
   if (gk && (c.image_h % gk || c.image_w % gk)) return "global_k must divide image_h and image_w";
+  const int64_t cpk = c.conv_proj_kernel, cps = c.conv_proj_stride;   // cvt.py:94-127
+  if (cpk < 0 || cps < 0 || (cpk == 0) != (cps == 0)) return "conv_proj_kernel and conv_proj_stride must both be positive or both be 0";
+  if (cpk && !nestb) return "conv_proj_kernel needs nest_block";
+  if (cpk && gk) return "conv_proj_kernel does not combine with global_k";
+  if (cpk && (c.patch_h != 1 || c.patch_w != 1)) return "conv_proj_kernel needs patch_h == patch_w == 1 (the tokens are the image_h x image_w map)";
   const int64_t pd = (int64_t)c.patch_h * c.patch_w * c.channels * (sd ? 5 : 1);   // SPT: the image and its four shifts (vit_for_small_dataset.py:154)
   int64_t off = 0, aoff = 0;
   auto add = [&](const std::string& n, std::vector<int64_t> s) {
@@ -84,6 +89,13 @@ std::string build_param_table(const vitx_config& c, std::vector<ParamDesc>& out)
       add(pre + ".attn.to_kv.kernel", {d, 2 * inner});
       add(pre + ".attn.mix_heads_pre_attn", {h, h});
       add(pre + ".attn.mix_heads_post_attn", {h, h});
+    } else if (cpk) {
+      for (const char* pj : {"to_q", "to_kv"}) {                     // cvt.py:84-86,103-104
+        const std::string q = pre + ".attn." + pj;
+        add(q + ".dw.kernel", {cpk, cpk, 1, d});
+        add(q + ".bn.gamma", {d}); add(q + ".bn.beta", {d}); add(q + ".bn.moving_mean", {d}); add(q + ".bn.moving_variance", {d});
+        add(q + ".pw.kernel", {d, pj[3] == 'q' ? inner : 2 * inner});
+      }
     } else if (gk) {
       add(pre + ".attn.to_q.kernel", {d, inner});                   // twins_svt.py:167
       add(pre + ".attn.to_kv.kernel", {gk * gk * d, 2 * inner});    // :168, the [k, k, d, 2 inner] kernel as rows in (p1 p2 c) order
@@ -227,7 +239,13 @@ static int dalloc(vitx_engine* e, void** p, size_t bytes, bool t_buffer, std::st
   } while (0)
 
 // global_k handles: keys per image = windows of the k-strided reduction of the image_h x image_w map (twins_svt.py:168)
-static inline int global_keys(const vitx_config& c) { return (c.image_h / c.global_k) * (c.image_w / c.global_k); }
+// conv_proj handles: positions of the 'SAME' convolution of stride conv_proj_stride over it (cvt.py:104)
+static inline int global_keys(const vitx_config& c) {
+  if (c.conv_proj_kernel) return (int)(ceil_div(c.image_h, c.conv_proj_stride) * ceil_div(c.image_w, c.conv_proj_stride));
+  return (c.image_h / c.global_k) * (c.image_w / c.global_k);
+}
+// handles whose keys are a reduction of the map: q and kv are projected apart (ba.q, ba.kv)
+static inline bool reduced_keys(const vitx_config& c) { return c.global_k != 0 || c.conv_proj_kernel != 0; }
 
 static int64_t find_param(const vitx_engine* e, const std::string& name) {
   for (auto& p : e->table)
@@ -1011,19 +1029,25 @@ static void attn_generic_bwd(vitx_engine* e, const BlockParams& bp, const AttnVi
 
 // nest_block handles: the plain-softmax form of the small-head kernels (attn_lsa.hip) where the fused kernels above do not apply
 static bool use_small_attn(const vitx_engine* e, int n) {
-  return e->cfg.nest_block && !e->cfg.global_k && e->small_attn && !e->force_generic_attn && attn_small_supported(n, e->cfg.dim_head);
+  return e->cfg.nest_block && !reduced_keys(e->cfg) && e->small_attn && !e->force_generic_attn && attn_small_supported(n, e->cfg.dim_head);
 }
 static bool use_fused_attn(const vitx_engine* e, int n) {
-  return e->bf16 && e->cfg.variant == VITX_VARIANT_VIT && !e->cfg.global_k && !e->force_generic_attn && attn_bf16_supported(n, e->cfg.dim_head);
+  return e->bf16 && e->cfg.variant == VITX_VARIANT_VIT && !reduced_keys(e->cfg) && !e->force_generic_attn && attn_bf16_supported(n, e->cfg.dim_head);
 }
-// global_k handles in the bf16 mode: the few-key kernels (attn_fewkey.hip) for at most 64 keys of dim_head 64
+// global_k and conv_proj handles in the bf16 mode: the few-key kernels (attn_fewkey.hip) for at most 64 keys of dim_head 64
 static bool use_fewkey_attn(const vitx_engine* e, int b, int nq, int nk) {
-  return e->cfg.global_k && e->bf16 && e->fewkey_attn && !e->force_generic_attn && (int64_t)b * e->cfg.heads <= 65535 &&
+  return reduced_keys(e->cfg) && e->bf16 && e->fewkey_attn && !e->force_generic_attn && (int64_t)b * e->cfg.heads <= 65535 &&
          attn_fewkey_supported(nq, nk, e->cfg.dim_head);
+}
+// conv_proj handles in the bf16 mode: the many-key kernels (attn_fewkey.hip) for 64 < keys <= MANYKEY_MAX of dim_head 64.  global_k handles
+// keep the materialised path above 64 keys.
+static bool use_manykey_attn(const vitx_engine* e, int b, int nq, int nk) {
+  return e->cfg.conv_proj_kernel && e->bf16 && e->manykey_attn && !e->force_generic_attn && (int64_t)b * e->cfg.heads <= 65535 &&
+         attn_manykey_supported(nq, nk, e->cfg.dim_head);
 }
 // BF16X3 mode: the fused split-operand attention (attn_x3.hip); VITX_X3_ATTN=2 keeps the materialised path with split-operand products, 0 exact ones
 static bool use_fused_attn_x3(const vitx_engine* e, int n) {
-  return e->x3 && e->x3_attn && e->x3_fused_attn && e->cfg.variant == VITX_VARIANT_VIT && !e->cfg.global_k && !e->force_generic_attn &&
+  return e->x3 && e->x3_attn && e->x3_fused_attn && e->cfg.variant == VITX_VARIANT_VIT && !reduced_keys(e->cfg) && !e->force_generic_attn &&
          attn_x3_supported(n, e->cfg.dim_head);
 }
 
@@ -1116,7 +1140,7 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
   const vitx_config& c = e->cfg;
   const int d = c.dim, inner = e->inner, m = c.mlp_dim, T = e->bf16, esz = e->esz;
   const int rows = b * nq;
-  const int nk = c.global_k ? global_keys(c) : nq + nc;   // (global_k handles: the keys are the reduced map)
+  const int nk = reduced_keys(c) ? global_keys(c) : nq + nc;   // (global_k / conv_proj handles: the keys are the reduced map)
   const double lnb = (double)rows * d * (4 + esz);
   if (!ba.skip_attn) {
   {
@@ -1146,6 +1170,22 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
     av.q = ba.q; av.ldq = inner; av.qb = (int64_t)nq * inner;
     av.k = ba.kv; av.ldk = 2 * inner; av.kb = (int64_t)nk * 2 * inner;
     av.v = boff(ba.kv, inner, esz); av.ldv = 2 * inner; av.vb = av.kb;       // cait.py:116
+  } else if (c.conv_proj_kernel) {
+    {   // cvt.py:84-85 of to_q (stride 1) and of to_kv (stride conv_proj_stride): depthwise convolution + BatchNormalization of the normalised map
+      Prof pr(e, "cvt_dwbn_fwd", 0, ((double)rows * d * 2 + (double)b * nk * d) * (esz + 8));
+      const float* P = e->params;
+      launch_cvt_dwbn_fwd(ba.y1, T, P + bp.cq.dw, P + bp.cq.gamma, P + bp.cq.beta, P + bp.cq.mmean, P + bp.cq.mvar, !e->bn_inference, e->bn_eps, ba.cq,
+                          ba.stq, ba.qin, d, e->cv_ws, b, c.image_h, c.image_w, d, c.conv_proj_kernel, 1, e->stream);
+      launch_cvt_dwbn_fwd(ba.y1, T, P + bp.ckv.dw, P + bp.ckv.gamma, P + bp.ckv.beta, P + bp.ckv.mmean, P + bp.ckv.mvar, !e->bn_inference, e->bn_eps, ba.ckv,
+                          ba.stkv, ba.ctx, d, e->cv_ws, b, c.image_h, c.image_w, d, c.conv_proj_kernel, c.conv_proj_stride, e->stream);
+    }
+    EpiParams ep; ep.out = ba.q; ep.ldo = inner;
+    dense_fwd(e, ba.qin, d, rows, bp.q, EPI_STORE, ep);                      // cvt.py:86 of to_q
+    EpiParams ep2; ep2.out = ba.kv; ep2.ldo = 2 * inner;
+    dense_fwd(e, ba.ctx, d, b * nk, bp.kv, EPI_STORE, ep2);                   // :86 of to_kv
+    av.q = ba.q; av.ldq = inner; av.qb = (int64_t)nq * inner;
+    av.k = ba.kv; av.ldk = 2 * inner; av.kb = (int64_t)nk * 2 * inner;
+    av.v = boff(ba.kv, inner, esz); av.ldv = 2 * inner; av.vb = av.kb;       // :116
   } else if (c.global_k) {
     EpiParams ep; ep.out = ba.q; ep.ldo = inner;
     dense_fwd(e, ba.y1, d, rows, bp.q, EPI_STORE, ep);                       // twins_svt.py:179
@@ -1184,10 +1224,14 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
     Prof pr(e, "attn_fewkey_fwd", 4.0 * b * c.heads * (double)nq * nk * c.dim_head, ((double)rows * inner * 2 + (double)b * nk * 2 * inner) * esz);
     launch_attn_fewkey_fwd((const bf16_t*)ba.q, (const bf16_t*)ba.kv, (bf16_t*)ba.o, ba.lse, b, nq, nk, c.heads, inner, 2 * inner, inner,
                            1.0f / std::sqrt((float)c.dim_head), e->stream);
+  } else if (use_manykey_attn(e, b, nq, nk)) {   // cvt.py:120-123
+    Prof pr(e, "attn_manykey_fwd", 4.0 * b * c.heads * (double)nq * nk * c.dim_head, ((double)rows * inner * 2 + (double)b * nk * 2 * inner) * esz);
+    launch_attn_manykey_fwd((const bf16_t*)ba.q, (const bf16_t*)ba.kv, (bf16_t*)ba.o, ba.lse, b, nq, nk, c.heads, inner, 2 * inner, inner,
+                            1.0f / std::sqrt((float)c.dim_head), e->stream);
   } else {
     const int need = c.variant == VITX_VARIANT_VIT ? 1 : 3;
     if (e->keep_scores && ba.sc_keep_elems == 0) {   // first use: this block's own score buffers, sized for the largest call
-      const int64_t emax = (int64_t)c.max_batch * c.heads * st.nq_max * round_up(c.global_k ? global_keys(c) : st.nq_max + st.nc_max, 4);
+      const int64_t emax = (int64_t)c.max_batch * c.heads * st.nq_max * round_up(reduced_keys(c) ? global_keys(c) : st.nq_max + st.nc_max, 4);
       if (e->sc_keep_bytes + need * emax * 4 <= e->sc_keep_budget) {
         for (int i = 0; i < need; ++i) DALLOC(ba.sc_keep[i], (size_t)emax * 4, false);
         ba.sc_keep_elems = emax;
@@ -1334,7 +1378,7 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
   BlockActs& ba = st.ba[l];
   const vitx_config& c = e->cfg;
   const int d = c.dim, inner = e->inner, m = c.mlp_dim, T = e->bf16, esz = e->esz;
-  const int rows = b * nq, nk = c.global_k ? global_keys(c) : nq + nc;
+  const int rows = b * nq, nk = reduced_keys(c) ? global_keys(c) : nq + nc;
   const void* gT = T ? e->g_lp : (const void*)e->g;   // T view of the residual gradient (re-read after each LayerNorm VJP: side_rotate)
   const double lnb = (double)rows * d * (4 + 4 + 4 + esz + esz);
   // Parallel half-blocks (parallel_vit.py:36-42): every branch of a group sees the SAME output gradient g, and the gradient of the
@@ -1546,6 +1590,48 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
     } else {
       launch_add_T(e->d_y, e->d_ctx, T, (int64_t)rows * d, e->stream);
     }
+  } else if (c.conv_proj_kernel) {
+    if (e->bn_inference) { err = "the saved forward ran BatchNormalization on the moving statistics (inference): it has no VJP"; return VITX_ERR_UNSUPPORTED; }
+    av.q = ba.q; av.ldq = inner; av.qb = (int64_t)nq * inner;
+    av.k = ba.kv; av.ldk = 2 * inner; av.kb = (int64_t)nk * 2 * inner;
+    av.v = boff(ba.kv, inner, esz); av.ldv = 2 * inner; av.vb = av.kb;
+    // d_qkv buffer as [dq | dkv], as CaiT's: dq [rows, inner], then dkv [b * nk, 2 * inner]
+    void* dq = e->d_qkv;
+    void* dkv = boff(e->d_qkv, (round_up((int64_t)rows, 256) + 320) * inner, esz);
+    ag.dq = dq; ag.lddq = inner; ag.dqb = (int64_t)nq * inner;
+    ag.dk = dkv; ag.lddk = 2 * inner; ag.dkb = (int64_t)nk * 2 * inner;
+    ag.dv = boff(dkv, inner, esz); ag.lddv = 2 * inner; ag.dvb = ag.dkb;
+    if (use_fewkey_attn(e, b, nq, nk)) {
+      Prof pr(e, "attn_fewkey_bwd", 10.0 * b * c.heads * (double)nq * nk * c.dim_head, ((double)rows * inner * 4 + (double)b * nk * 4 * inner) * esz);
+      launch_attn_fewkey_bwd((const bf16_t*)ba.q, (const bf16_t*)ba.kv, (const bf16_t*)ba.o, (const bf16_t*)d_o, ba.lse, (bf16_t*)dq, (bf16_t*)dkv, b, nq, nk,
+                             c.heads, inner, 2 * inner, inner, inner, inner, 2 * inner, 1.0f / std::sqrt((float)c.dim_head), e->stream);
+    } else if (use_manykey_attn(e, b, nq, nk)) {
+      Prof pr(e, "attn_manykey_bwd", 14.0 * b * c.heads * (double)nq * nk * c.dim_head, ((double)rows * inner * 7 + (double)b * nk * 6 * inner) * esz);
+      launch_attn_manykey_bwd((const bf16_t*)ba.q, (const bf16_t*)ba.kv, (const bf16_t*)ba.o, (const bf16_t*)d_o, ba.lse, (bf16_t*)dq, (bf16_t*)dkv, b, nq, nk,
+                              c.heads, inner, 2 * inner, inner, inner, inner, 2 * inner, 1.0f / std::sqrt((float)c.dim_head), e->stream);
+    } else {
+      int rc = ensure_scores(e, 4, (int64_t)b * c.heads * nq * round_up(nk, 4), err);
+      if (rc != VITX_OK) return rc;
+      attn_generic_bwd(e, bp, av, ag, b, &ba);
+    }
+    // pointwise VJPs: d(q_in) into d_y, d(kv_in) into d_ctx; then BatchNormalization and the depthwise convolutions back onto the map (cvt.py:84-86)
+    EpiParams ep; ep.out = e->d_y; ep.ldo = d;
+    const hipEvent_t fork_qkv = side_prefork(e);                                // dq and dkv are complete
+    dense_dgrad(e, dq, inner, rows, bp.q, EPI_STORE, ep);
+    dense_wgrad(e, ba.qin, d, dq, inner, rows, bp.q, fork_qkv);
+    EpiParams ep2; ep2.out = e->d_ctx; ep2.ldo = d;
+    dense_dgrad(e, dkv, 2 * inner, b * nk, bp.kv, EPI_STORE, ep2);
+    dense_wgrad(e, ba.ctx, d, dkv, 2 * inner, b * nk, bp.kv, fork_qkv);
+    side_note_read(e, e->rg_dqkv);
+    Prof pr(e, "cvt_dwbn_bwd", 0, ((double)rows * d * 3 + (double)b * nk * d * 2) * (esz + 8));
+    const float* P = e->params;
+    float* G = e->grads;
+    const int k = c.conv_proj_kernel, st = c.conv_proj_stride;
+    launch_cvt_bn_bwd(e->d_y, T, d, ba.cq, ba.stq, P + bp.cq.gamma, G + bp.cq.gamma, G + bp.cq.beta, e->cv_dq, e->cv_ws, rows, d, e->stream);
+    launch_cvt_bn_bwd(e->d_ctx, T, d, ba.ckv, ba.stkv, P + bp.ckv.gamma, G + bp.ckv.gamma, G + bp.ckv.beta, e->cv_dkv, e->cv_ws, (int64_t)b * nk, d, e->stream);
+    launch_cvt_dw_bwd_dkern(ba.y1, T, e->cv_dq, e->cv_ws, G + bp.cq.dw, b, c.image_h, c.image_w, d, k, 1, e->stream);
+    launch_cvt_dw_bwd_dkern(ba.y1, T, e->cv_dkv, e->cv_ws, G + bp.ckv.dw, b, c.image_h, c.image_w, d, k, st, e->stream);
+    launch_cvt_dw_bwd_dx(e->cv_dq, P + bp.cq.dw, e->cv_dkv, P + bp.ckv.dw, st, e->d_y, T, b, c.image_h, c.image_w, d, k, e->stream);
   } else if (c.global_k) {
     av.q = ba.q; av.ldq = inner; av.qb = (int64_t)nq * inner;
     av.k = ba.kv; av.ldk = 2 * inner; av.kb = (int64_t)nk * 2 * inner;
@@ -1789,6 +1875,17 @@ static int engine_create_body(vitx_engine* e, const vitx_config& cfg, std::strin
         }
         bp.mix_pre = find_param(e, pre + ".attn.mix_heads_pre_attn");
         bp.mix_post = find_param(e, pre + ".attn.mix_heads_post_attn");
+      } else if (c.conv_proj_kernel) {
+        if ((rc = init_dense(e, bp.q, pre + ".attn.to_q.pw.kernel", "", d, inner, err)) != VITX_OK) return rc;
+        if ((rc = init_dense(e, bp.kv, pre + ".attn.to_kv.pw.kernel", "", d, 2 * inner, err)) != VITX_OK) return rc;
+        for (int pj = 0; pj < 2; ++pj) {
+          ConvProj& cp = pj ? bp.ckv : bp.cq;
+          const std::string q = pre + (pj ? ".attn.to_kv" : ".attn.to_q");
+          cp.dw = find_param(e, q + ".dw.kernel");
+          cp.gamma = find_param(e, q + ".bn.gamma"); cp.beta = find_param(e, q + ".bn.beta");
+          cp.mmean = find_param(e, q + ".bn.moving_mean"); cp.mvar = find_param(e, q + ".bn.moving_variance");
+          if (cp.dw < 0 || cp.gamma < 0 || cp.beta < 0 || cp.mmean < 0 || cp.mvar < 0) { err = "missing parameter under " + q; return VITX_ERR_INVALID; }
+        }
       } else if (c.global_k) {
         if ((rc = init_dense(e, bp.q, pre + ".attn.to_q.kernel", "", d, inner, err)) != VITX_OK) return rc;
         if ((rc = init_dense(e, bp.kv, pre + ".attn.to_kv.kernel", "", c.global_k * c.global_k * d, 2 * inner, err)) != VITX_OK) return rc;
@@ -1824,6 +1921,18 @@ static int engine_create_body(vitx_engine* e, const vitx_config& cfg, std::strin
         if (nc > 0) DALLOC(ba.ctx, (size_t)crow * d * esz, true);
         DALLOC(ba.fa, (size_t)rows * d * esz, true);
         DALLOC(ba.fm, (size_t)rows * d * esz, true);
+      } else if (c.conv_proj_kernel) {
+        // the inputs of the pointwise projections (qin, ctx: behind BatchNormalization, T), q and kv, and what the VJP re-reads: the fp32
+        // convolution outputs and the (mean | rstd) they were normalised with
+        const int64_t krow = round_up(B * global_keys(c), 256) + 320;
+        DALLOC(ba.q, (size_t)rows * inner * esz, true);
+        DALLOC(ba.kv, (size_t)krow * 2 * inner * esz, true);
+        DALLOC(ba.qin, (size_t)rows * d * esz, true);
+        DALLOC(ba.ctx, (size_t)krow * d * esz, true);
+        DALLOC(ba.cq, (size_t)rows * d * 4, false);
+        DALLOC(ba.ckv, (size_t)krow * d * 4, false);
+        DALLOC(ba.stq, (size_t)2 * d * 8, false);
+        DALLOC(ba.stkv, (size_t)2 * d * 8, false);
       } else if (c.global_k) {
         // q of every token; the k-unfolded LayerNorm output (ctx) and kv of the reduced map: (image_h / k)(image_w / k) rows per image
         const int64_t krow = round_up(B * global_keys(c), 256) + 320;
@@ -1977,6 +2086,11 @@ static int engine_create_body(vitx_engine* e, const vitx_config& cfg, std::strin
   const int64_t dctx_elems = std::max<int64_t>(crow_max * d, c.global_k ? (round_up(B * global_keys(c), 256) + 320) * kfeat : 0);
   DALLOC(e->d_ctx, (size_t)dctx_elems * esz, true);
   DALLOC(e->d_br, (size_t)rmax * d * esz, true);
+  if (c.conv_proj_kernel) {   // fp32 d(convolution output) of the two projections; slice partials of their sums
+    DALLOC(e->cv_dq, (size_t)rmax * d * 4, false);
+    DALLOC(e->cv_dkv, (size_t)(round_up(B * global_keys(c), 256) + 320) * d * 4, false);
+    DALLOC(e->cv_ws, (size_t)cvt_dwbn_ws_elems(d, c.conv_proj_kernel) * 4, false);
+  }
   if (e->side) {
     // ring slots of the buffers the input-gradient chain rewrites while side-stream weight gradients read them (slot 0 = the buffer above)
     auto ring = [&](SideRing& r, void* first, size_t bytes, int n) -> int {
@@ -2525,7 +2639,7 @@ int engine_transformer_forward(vitx_engine* e, const float* tokens_dev, int b, i
   if (c.variant == VITX_VARIANT_CAIT || c.variant == VITX_VARIANT_PATCH_MERGER) { err = "transformer_forward: ViT / DeepViT only"; return VITX_ERR_UNSUPPORTED; }
   if (c.small_dataset) { err = "transformer_forward: not for small_dataset handles"; return VITX_ERR_UNSUPPORTED; }
   if (b <= 0 || b > c.max_batch || n <= 0 || n > e->ntok_cap) { err = "transformer_forward: b or n out of range"; return VITX_ERR_INVALID; }
-  if (c.global_k && n != c.image_h * c.image_w) { err = "transformer_forward: a global_k handle takes image_h * image_w tokens per sequence"; return VITX_ERR_INVALID; }
+  if (reduced_keys(c) && n != c.image_h * c.image_w) { err = "transformer_forward: a global_k / conv_proj handle takes image_h * image_w tokens per sequence"; return VITX_ERR_INVALID; }
   Stage& s0 = e->stages[0];
   if (l1 < 0) l1 = s0.depth;
   if (l0 < 0 || l0 > l1 || l1 > s0.depth) { err = "transformer_forward: layer range out of bounds"; return VITX_ERR_INVALID; }

@@ -157,6 +157,16 @@ void launch_attn_fewkey_fwd(const bf16_t* q, const bf16_t* kv, bf16_t* o, float*
 void launch_attn_fewkey_bwd(const bf16_t* q, const bf16_t* kv, const bf16_t* o, const bf16_t* d_o, const float* lse, bf16_t* dq, bf16_t* dkv, int b, int nq,
                             int nk, int heads, int64_t ldq, int64_t ldkv, int64_t ldo, int64_t lddo, int64_t lddq, int64_t lddkv, float scale, hipStream_t s);
 
+// 64 < nk <= MANYKEY_MAX keys (cvt.py:120-123), same layouts and lse: the forward keeps all of K and V in LDS and walks 64-key chunks with an
+// online softmax; the VJP is two launches -- d(k) / d(v) per 64-key chunk (the few-key kernel with a key offset), then d(q) with all keys in LDS.
+// MANYKEY_MAX is what the d(q) kernel's K, V and K^T fit of the 160 KiB of LDS (attn_fewkey.hip asserts it).
+constexpr int MANYKEY_MAX = 320;
+bool attn_manykey_supported(int nq, int nk, int dim_head);
+void launch_attn_manykey_fwd(const bf16_t* q, const bf16_t* kv, bf16_t* o, float* lse, int b, int nq, int nk, int heads, int64_t ldq, int64_t ldkv,
+                             int64_t ldo, float scale, hipStream_t s);
+void launch_attn_manykey_bwd(const bf16_t* q, const bf16_t* kv, const bf16_t* o, const bf16_t* d_o, const float* lse, bf16_t* dq, bf16_t* dkv, int b, int nq,
+                             int nk, int heads, int64_t ldq, int64_t ldkv, int64_t ldo, int64_t lddo, int64_t lddq, int64_t lddkv, float scale, hipStream_t s);
+
 // ---------------------------------------------------------------- twins_ops.hip
 // TwinsSVT PatchEmbedding's Rearrange (twins_svt.py:103): out[(b h w), (c p1 p2)] = x[b, h p + p1, w p + p2, c] (row stride ld), and its VJP,
 // the inverse permutation (every element of dx written)
@@ -173,6 +183,24 @@ void launch_twins_peg_fwd(const float* x, const float* kern, const float* bias, 
 void launch_twins_peg_bwd_dx(const float* dy, const float* kern, float* dx, int b, int H, int W, int C, int kp, hipStream_t s);
 int64_t twins_peg_ws_elems(int C, int kp);
 void launch_twins_peg_bwd_dkern(const float* x, const float* dy, float* ws, float* dkern, int b, int H, int W, int C, int kp, hipStream_t s);
+
+// ---------------------------------------------------------------- cvt_ops.hip
+// CvT's convolutional projection in front of its pointwise Dense (cvt.py:84-85): depthwise Conv2D(k, stride st, 'SAME', no bias) with kern
+// [k, k, 1, C] on x [b, H, W, C] NHWC in the storage type, then BatchNormalization over all b * oh * ow positions.  conv [b, oh, ow, C] (fp32)
+// and stats [2 C] = (mean | rstd) (double, as every sum behind them) are kept for the VJP; y [b * oh * ow, ldy] is the normalised result in the storage type.  training == 0
+// normalises with mov_mean / mov_var.  ws: cvt_dwbn_ws_elems floats.  Every sum is fixed-slice partials added in order (no atomics).
+int64_t cvt_dwbn_ws_elems(int C, int k);
+void launch_cvt_dwbn_fwd(const void* x, int is_bf16, const float* kern, const float* gamma, const float* beta, const float* mov_mean, const float* mov_var,
+                         int training, float eps, float* conv, double* stats, void* y, int64_t ldy, float* ws, int b, int H, int W, int C, int k, int st,
+                         hipStream_t s);
+// BatchNorm VJP on batch statistics: dgamma = sum dy xhat, dbeta = sum dy, dconv = gamma rstd (dy - dbeta / N - xhat dgamma / N) (fp32)
+void launch_cvt_bn_bwd(const void* dy, int is_bf16, int64_t lddy, const float* conv, const double* stats, const float* gamma, float* dgamma, float* dbeta,
+                       float* dconv, float* ws, int64_t rows, int C, hipStream_t s);
+// d(kern) [k, k, 1, C] from the convolution's input and dconv
+void launch_cvt_dw_bwd_dkern(const void* x, int is_bf16, const float* dconv, float* ws, float* dkern, int b, int H, int W, int C, int k, int st, hipStream_t s);
+// d(x) [b, H, W, C] in the storage type, every element written once: the q projection's share (stride 1) plus the kv projection's (stride st_kv)
+void launch_cvt_dw_bwd_dx(const float* dconv_q, const float* kern_q, const float* dconv_kv, const float* kern_kv, int st_kv, void* dx, int is_bf16, int b, int H,
+                          int W, int C, int k, hipStream_t s);
 
 // ---------------------------------------------------------------- elementwise.hip
 void launch_unfold(const float* img, void* out, int out_bf16, int b, int H, int W, int C, int ph, int pw,

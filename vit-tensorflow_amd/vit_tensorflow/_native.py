@@ -24,13 +24,15 @@ class VitxError(RuntimeError):
 
 
 class _ConfigFlags(C.Structure):
-    _fields_ = [("cct_block", C.c_int32), ("nest_block", C.c_int32), ("global_k", C.c_int32)]
+    _fields_ = [("cct_block", C.c_int32), ("nest_block", C.c_int32), ("global_k", C.c_int32),
+                ("conv_proj_kernel", C.c_int16), ("conv_proj_stride", C.c_int16)]
 
 
 class _ConfigTail(C.Union):
-    """The last four words of vitx_config.  include/vitx.h carved cct_block, nest_block and global_k out of the first three reserved words;
-    `reserved` keeps its four-word view here (reserved[0] is cct_block, reserved[1] nest_block, reserved[2] global_k), so code that zeroes or
-    inspects it by that name sees the layout it always saw."""
+    """The last four words of vitx_config.  include/vitx.h carved cct_block, nest_block and global_k out of the first three reserved words and
+    conv_proj_kernel / conv_proj_stride (two halves) out of the last; `reserved` keeps its four-word view here (reserved[0] is cct_block,
+    reserved[1] nest_block, reserved[2] global_k, reserved[3] the two conv_proj halves), so code that zeroes or inspects it by that name sees
+    the layout it always saw.  The struct has no spare word left."""
     _anonymous_ = ("_flags",)
     _fields_ = [("reserved", C.c_int32 * 4), ("_flags", _ConfigFlags)]
 
@@ -112,6 +114,16 @@ class TwinsConfig(C.Structure):
         ("depth", C.c_int32 * 4), ("peg_kernel_size", C.c_int32),
         ("ln_eps", C.c_float), ("compute", C.c_int32), ("max_batch", C.c_int32), ("device_id", C.c_int32),
         ("fused_global_attn", C.c_int32), ("reserved", C.c_int32 * 7),
+    ]
+
+
+class CvTConfig(C.Structure):
+    _fields_ = [
+        ("image_h", C.c_int32), ("image_w", C.c_int32), ("num_classes", C.c_int32),
+        ("emb_dim", C.c_int32 * 3), ("emb_kernel", C.c_int32 * 3), ("emb_stride", C.c_int32 * 3), ("proj_kernel", C.c_int32 * 3),
+        ("kv_proj_stride", C.c_int32 * 3), ("heads", C.c_int32 * 3), ("depth", C.c_int32 * 3), ("mlp_mult", C.c_int32 * 3),
+        ("ln_eps", C.c_float), ("bn_eps", C.c_float), ("compute", C.c_int32), ("max_batch", C.c_int32), ("device_id", C.c_int32),
+        ("fused_attn", C.c_int32), ("reserved", C.c_int32 * 8),
     ]
 
 
@@ -298,6 +310,23 @@ SYMBOLS: List[Tuple[str, object, list]] = [
     ("vitx_twins_profile_begin", C.c_int32, [C.c_void_p]),
     ("vitx_twins_profile_end", C.c_int32, [C.c_void_p, _P(KernelStat), C.c_int32, _P(C.c_int32)]),
     ("vitx_twins_read", C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, _P(C.c_int64)]),
+    ("vitx_cvt_param_table_size", C.c_int32, [_P(CvTConfig), _P(C.c_int64), _P(C.c_int64)]),
+    ("vitx_cvt_param_table_entry", C.c_int32, [_P(CvTConfig), C.c_int64, C.c_char_p, C.c_int32, _P(C.c_int64), _P(C.c_int32), _P(C.c_int64)]),
+    ("vitx_cvt_create", C.c_int32, [_P(CvTConfig), _P(C.c_void_p)]),
+    ("vitx_cvt_destroy", C.c_int32, [C.c_void_p]),
+    ("vitx_cvt_set_params", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_cvt_get_params", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_cvt_get_grads", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_cvt_params_dev", C.c_int32, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)]),
+    ("vitx_cvt_grads_dev", C.c_int32, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)]),
+    ("vitx_cvt_params_changed", C.c_int32, [C.c_void_p]),
+    ("vitx_cvt_forward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    ("vitx_cvt_forward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    ("vitx_cvt_backward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("vitx_cvt_backward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("vitx_cvt_profile_begin", C.c_int32, [C.c_void_p]),
+    ("vitx_cvt_profile_end", C.c_int32, [C.c_void_p, _P(KernelStat), C.c_int32, _P(C.c_int32)]),
+    ("vitx_cvt_read", C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, _P(C.c_int64)]),
 ]
 
 _lib = None
@@ -364,6 +393,11 @@ def nest_param_table(cfg: NesTConfig):
 def twins_param_table(cfg: TwinsConfig):
     """[(name, shape, offset)] of TwinsSVT's variables from the C library (host-only call; no GPU needed)."""
     return table_of("vitx_twins", C.byref(cfg))
+
+
+def cvt_param_table(cfg: CvTConfig):
+    """[(name, shape, offset)] of CvT's variables from the C library (host-only call; no GPU needed)."""
+    return table_of("vitx_cvt", C.byref(cfg))
 
 
 def mim_param_table(handle, prefix="vitx_mim"):
