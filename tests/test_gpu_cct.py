@@ -130,7 +130,10 @@ def test_sine_matches_restatement():
     assert "classifier.positional_emb" not in P
     img, dl = _inputs(kw, 2, 4)
     rl, rg, rd = R.forward_backward(kw, P, img, dl)
-    _check_fp32("sine", _model(kw, "fp32", 2, P), img, dl, rl, rg, rd)
+    m = _model(kw, "fp32", 2, P)
+    _check_fp32("sine", m, img, dl, rl, rg, rd)
+    prof = m.profile(lambda: (m(img, training=False), m.backward(dl, want_dimg=True)))   # {class: (launches, total_ms)}
+    assert prof["cct_im2col"][0] > 0 and prof["cct_conv_gemm"][0] > 0, prof
 
 
 # kernel edges through a one-block model, fp32, against the restatement.  Conv k3 s1 keeps the extent, so the 3/2 pool sees the image's extents:

@@ -140,8 +140,7 @@ struct vitx_cct {
   int64_t n_params = 0, n_arena = 0;
   float *params = nullptr, *grads = nullptr;
   vitx_engine* eng = nullptr;
-  std::vector<std::pair<int64_t, int64_t>> maps;   // (composite arena offset, engine arena offset) per engine tensor, with its element count below
-  std::vector<int64_t> map_count;
+  std::vector<ArenaMap> maps;   // the block tensors -> the engine's
   std::vector<ConvLayer> conv;
   int64_t pool_w = -1, pool_b = -1, pos = -1, norm_g = -1, norm_b = -1, fc_w = -1, fc_b = -1;
   int n = 0, d = 0, nc = 0, B = 0, x3 = 0;
@@ -276,23 +275,15 @@ int cct_create(const vitx_cct_config& cin, vitx_cct** out, std::string& err) {
   m->x3 = c.compute == VITX_COMPUTE_FP32_PARITY ? 0 : 1;
   if ((rc = engine_create(cct_engine_config(c, m->n), &m->eng, err)) != VITX_OK) return fail(rc);
   m->stream = m->eng->stream;
-  // parameter maps: every block tensor is one contiguous copy
+  // parameter maps: every block tensor is one contiguous run
   static const char* PAIRS[][2] = {{"pre_norm.gamma", "attn.norm.gamma"}, {"pre_norm.beta", "attn.norm.beta"}, {"self_attn.to_qkv.kernel", "attn.to_qkv.kernel"},
                                    {"self_attn.proj.kernel", "attn.to_out.kernel"}, {"self_attn.proj.bias", "attn.to_out.bias"},
                                    {"linear1.kernel", "mlp.fc1.kernel"}, {"linear1.bias", "mlp.fc1.bias"}, {"norm1.gamma", "mlp.norm.gamma"},
                                    {"norm1.beta", "mlp.norm.beta"}, {"linear2.kernel", "mlp.fc2.kernel"}, {"linear2.bias", "mlp.fc2.bias"}};
-  auto find = [](const std::vector<ParamDesc>& t, const std::string& n) -> const ParamDesc* {
-    for (const auto& p : t) if (p.name == n) return &p;
-    return nullptr;
-  };
   for (int l = 0; l < c.num_layers; ++l)
-    for (const auto& pr : PAIRS) {
-      const ParamDesc* cp = find(m->table, "classifier.blocks." + std::to_string(l) + "." + pr[0]);
-      const ParamDesc* ep = find(m->eng->table, "transformer." + std::to_string(l) + "." + pr[1]);
-      if (!cp || !ep || cp->count != ep->count) { err = std::string("internal: parameter map ") + pr[0] + " -> " + pr[1]; return fail(VITX_ERR_INVALID); }
-      m->maps.push_back({cp->aoff, ep->aoff});
-      m->map_count.push_back(cp->count);
-    }
+    for (const auto& pr : PAIRS)
+      if ((rc = add_arena_map(m->maps, m->table, "classifier.blocks." + std::to_string(l) + "." + pr[0], m->eng->table,
+                              "transformer." + std::to_string(l) + "." + pr[1], err)) != VITX_OK) return fail(rc);
   // buffers
   const int64_t B = m->B, n = m->n, d = m->d;
   CALLOC(m->params, m->n_arena);
@@ -337,15 +328,9 @@ int cct_create(const vitx_cct_config& cin, vitx_cct** out, std::string& err) {
 }
 
 int push_params(vitx_cct* m, std::string& err) {
-  for (size_t i = 0; i < m->maps.size(); ++i)
-    HIPCHK(hipMemcpyAsync(m->eng->params + m->maps[i].second, m->params + m->maps[i].first, (size_t)m->map_count[i] * 4, hipMemcpyDeviceToDevice, m->stream));
-  m->eng->params_dirty = true;
-  return VITX_OK;
-}
-int pull_grads(vitx_cct* m, std::string& err) {
-  for (size_t i = 0; i < m->maps.size(); ++i)
-    HIPCHK(hipMemcpyAsync(m->grads + m->maps[i].first, m->eng->grads + m->maps[i].second, (size_t)m->map_count[i] * 4, hipMemcpyDeviceToDevice, m->stream));
-  return VITX_OK;
+  const int rc = copy_maps(m->params, m->eng->params, m->maps, true, m->stream, err);
+  if (rc == VITX_OK) m->eng->params_dirty = true;
+  return rc;
 }
 
 int cct_forward(vitx_cct* m, const float* img_dev, int b, std::string& err) {
@@ -420,7 +405,7 @@ int cct_backward(vitx_cct* m, const float* dlogits_dev, float* dimg_dev, std::st
   // blocks
   int rc;
   if ((rc = engine_transformer_backward(m->eng, m->denc, m->dtok, err)) != VITX_OK) return rc;
-  if ((rc = pull_grads(m, err)) != VITX_OK) return rc;
+  if ((rc = copy_maps(m->grads, m->eng->grads, m->maps, false, m->stream, err)) != VITX_OK) return rc;
   if (c.positional_embedding == VITX_CCT_POS_LEARNABLE) launch_batch_reduce(m->dtok, b, n, d, 0, n, G + m->pos, s);
   // tokenizer, last layer first
   const float* dpool = m->dtok;
@@ -460,26 +445,13 @@ int cct_backward(vitx_cct* m, const float* dlogits_dev, float* dimg_dev, std::st
 extern "C" {
 
 int32_t vitx_cct_param_table_size(const vitx_cct_config* cfg, int64_t* n_tensors, int64_t* n_elems) {
-  CAPI_TRY
   if (!cfg) return capi_fail(VITX_ERR_INVALID, "null argument");
-  std::vector<ParamDesc> t;
-  int64_t n = 0;
-  std::string e = cct_param_table(*cfg, t, &n, nullptr);
-  if (!e.empty()) return capi_fail(VITX_ERR_INVALID, e);
-  if (n_tensors) *n_tensors = (int64_t)t.size();
-  if (n_elems) *n_elems = n;
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_table_size(*cfg, n_tensors, n_elems, cct_param_table);
 }
 int32_t vitx_cct_param_table_entry(const vitx_cct_config* cfg, int64_t index, char* name, int32_t name_cap, int64_t shape[4], int32_t* rank,
                                    int64_t* offset_elems) {
-  CAPI_TRY
   if (!cfg) return capi_fail(VITX_ERR_INVALID, "null argument");
-  std::vector<ParamDesc> t;
-  std::string e = cct_param_table(*cfg, t, nullptr, nullptr);
-  if (!e.empty()) return capi_fail(VITX_ERR_INVALID, e);
-  return write_table_entry(t, index, name, name_cap, shape, rank, offset_elems);
-  CAPI_CATCH
+  return composite_table_entry(*cfg, index, name, name_cap, shape, rank, offset_elems, cct_param_table);
 }
 int32_t vitx_cct_sequence_length(const vitx_cct_config* cfg, int32_t* n_tokens) {
   CAPI_TRY
@@ -492,15 +464,8 @@ int32_t vitx_cct_sequence_length(const vitx_cct_config* cfg, int32_t* n_tokens) 
   CAPI_CATCH
 }
 int32_t vitx_cct_create(const vitx_cct_config* cfg, vitx_cct_handle* out) {
-  CAPI_TRY
   if (!cfg || !out) return capi_fail(VITX_ERR_INVALID, "null argument");
-  std::string err;
-  vitx_cct* m = nullptr;
-  int rc = cct_create(*cfg, &m, err);
-  if (rc != VITX_OK) return capi_fail(rc, err);
-  *out = m;
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_create(*cfg, out, cct_create);
 }
 int32_t vitx_cct_destroy(vitx_cct_handle m) {
   CAPI_TRY
@@ -524,17 +489,9 @@ int32_t vitx_cct_forward_dev(vitx_cct_handle m, const float* img_dev, int32_t b,
   CAPI_CATCH
 }
 int32_t vitx_cct_forward(vitx_cct_handle m, const float* img_host, int32_t b, float* logits_host) {
-  CAPI_TRY
   if (!m || !img_host || !logits_host) return capi_fail(VITX_ERR_INVALID, "null argument");
-  if (b <= 0 || b > m->cfg.max_batch) return capi_fail(VITX_ERR_INVALID, "batch must be in [1, max_batch]");
-  CAPI_HIP(hipMemcpyAsync(m->img, img_host, (size_t)b * m->cfg.img_height * m->cfg.img_width * m->cfg.n_input_channels * 4, hipMemcpyHostToDevice, m->stream));
-  std::string err;
-  int rc = cct_forward(m, m->img, b, err);
-  if (rc != VITX_OK) return capi_fail(rc, err);
-  CAPI_HIP(hipMemcpyAsync(logits_host, m->logits, (size_t)b * m->nc * 4, hipMemcpyDeviceToHost, m->stream));
-  CAPI_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_forward_host(m, img_host, (int64_t)m->cfg.img_height * m->cfg.img_width * m->cfg.n_input_channels, b, logits_host,
+                                [&](std::string& err) { return cct_forward(m, m->img, b, err); });
 }
 int32_t vitx_cct_backward_dev(vitx_cct_handle m, const float* dlogits_dev, float* dimg_dev_or_null) {
   CAPI_TRY
@@ -546,27 +503,17 @@ int32_t vitx_cct_backward_dev(vitx_cct_handle m, const float* dlogits_dev, float
   CAPI_CATCH
 }
 int32_t vitx_cct_backward(vitx_cct_handle m, const float* dlogits_host, float* dimg_host_or_null) {
-  CAPI_TRY
   if (!m || !dlogits_host) return capi_fail(VITX_ERR_INVALID, "null argument");
-  if (!m->have_fwd) return capi_fail(VITX_ERR_STATE, "backward requires a preceding forward");
-  CAPI_HIP(hipMemcpyAsync(m->dlogits, dlogits_host, (size_t)m->b * m->nc * 4, hipMemcpyHostToDevice, m->stream));
-  std::string err;
-  int rc = cct_backward(m, m->dlogits, dimg_host_or_null ? m->dimg : nullptr, err);
-  if (rc != VITX_OK) return capi_fail(rc, err);
-  if (dimg_host_or_null)
-    CAPI_HIP(hipMemcpyAsync(dimg_host_or_null, m->dimg, (size_t)m->b * m->cfg.img_height * m->cfg.img_width * m->cfg.n_input_channels * 4, hipMemcpyDeviceToHost,
-                         m->stream));
-  CAPI_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_backward_host(m, dlogits_host, dimg_host_or_null, (int64_t)m->cfg.img_height * m->cfg.img_width * m->cfg.n_input_channels,
+                                 [&](float* dimg_dev, std::string& err) { return cct_backward(m, m->dlogits, dimg_dev, err); });
 }
 int32_t vitx_cct_profile_begin(vitx_cct_handle m) {
   if (!m) return capi_fail(VITX_ERR_INVALID, "null handle");
-  return vitx_profile_begin(m->eng);
+  return composite_profile_begin({m->eng});
 }
 int32_t vitx_cct_profile_end(vitx_cct_handle m, vitx_kernel_stat* out, int32_t cap, int32_t* n_out) {
   if (!m) return capi_fail(VITX_ERR_INVALID, "null handle");
-  return vitx_profile_end(m->eng, out, cap, n_out);
+  return composite_profile_end({m->eng}, out, cap, n_out);
 }
 int32_t vitx_cct_read(vitx_cct_handle m, const char* which, float* out_host, int64_t cap, int64_t* n_elems) {
   CAPI_TRY
@@ -580,11 +527,7 @@ int32_t vitx_cct_read(vitx_cct_handle m, const char* which, float* out_host, int
   else if (w == "pool_weights") { src = m->p; n = (int64_t)m->b * m->n; }
   else if (w == "pooled") { src = m->pooled; n = (int64_t)m->b * m->d; }
   else return capi_fail(VITX_ERR_INVALID, "unknown tensor name");
-  if (n_elems) *n_elems = n;
-  if (n > cap) return capi_fail(VITX_ERR_INVALID, "output buffer too small");
-  CAPI_HIP(hipMemcpyAsync(out_host, src, (size_t)n * 4, hipMemcpyDeviceToHost, m->stream));
-  CAPI_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
+  return composite_read_tail(src, n, out_host, cap, n_elems, m->stream);
   CAPI_CATCH
 }
 

@@ -1,6 +1,6 @@
-// What the composites with a 'SAME' convolution share (cct.hip: the tokenizer; nest.hip: Aggregate): the convolution is im2col rows (cct_tok.hip)
+// What the composites with a 'SAME' convolution share (cct.hip: the tokenizer; nest.hip: Aggregate; cvt.hip: the stage embedding): the convolution is im2col rows (cct_tok.hip)
 // times the HWIO kernel viewed as [k*k*Cin, Cout] on the GEMM launchers, in image chunks so that the row workspace is bounded.  Here: the
-// weight-gradient product, the chunk accumulation, the workspace budget of one chunk, and the profiler scope of a composite's own launches.
+// weight-gradient product, the chunk accumulation and the workspace budget of one chunk.
 #pragma once
 #include "composite.h"
 
@@ -9,26 +9,6 @@ static __global__ void conv_accum_kernel(float* __restrict__ dst, const float* _
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < n) dst[e] = first ? src[e] : dst[e] + src[e];
 }
-
-// a launch (or a group of launches) booked under a kernel class of an engine's profiler (vitx_cct_profile_* / vitx_nest_profile_*)
-struct CompositeProf {
-  vitx_engine* e;
-  ProfEvent pe{};
-  bool on;
-  CompositeProf(vitx_engine* e_, const char* name) : e(e_), on(e_->profiling) {
-    if (!on) return;
-    pe.cls = prof_class(e, name);
-    pe.cls2 = -1; pe.flops = 0; pe.bytes = 0;
-    (void)hipEventCreate(&pe.e0);
-    (void)hipEventCreate(&pe.e1);
-    (void)hipEventRecord(pe.e0, e->stream);
-  }
-  ~CompositeProf() {
-    if (!on) return;
-    (void)hipEventRecord(pe.e1, e->stream);
-    e->prof_events.push_back(pe);
-  }
-};
 
 // Weight gradient of a convolution: dWp[Kp, N] = rows[M, Kp]^T dY[M, N] over all Kp (>= 64) padded columns.  On the split-operand kernel the M token
 // rows are cut into slices (the kernel's batch index, the last one shorter) so that tiles x slices fills the chip; the fp32 partials are summed in

@@ -213,17 +213,13 @@ struct XLayer {
   float *x0 = nullptr, *xin = nullptr, *xn = nullptr, *mean = nullptr, *rstd = nullptr, *q_act = nullptr, *kv_act = nullptr, *o = nullptr, *lse = nullptr,
         *fd = nullptr;
 };
-// composite arena <-> engine arena: `rows` rows of `width` elements
-struct XMap { int eng; int64_t coff, ldc, eoff, lde, width, rows; };
-
 struct vitx_crossvit {
   vitx_crossvit_config cfg{};
   std::vector<ParamDesc> table;
   int64_t n_params = 0, n_arena = 0;
   float *params = nullptr, *grads = nullptr;
   std::vector<vitx_engine*> eng;      // [br * depth + i]: the encoder of branch br in multi-scale layer i
-  std::vector<XMap> maps;
-  std::vector<std::vector<int>> eng_maps, head_maps;   // per engine: map indices of its encoder (+ embedder) / of its mlp_head
+  std::vector<std::vector<ArenaMap>> eng_maps, head_maps;   // per engine: the maps of its encoder (+ embedder) / of its mlp_head
   std::vector<XLayer> xl;             // [(i * cross_depth + k) * 2 + dir]
   int64_t fn_g[2][64] = {}, fn_b[2][64] = {};   // per branch / layer: the encoder's final LayerNorm
   int dim[2] = {0, 0}, np_max[2] = {0, 0}, patch[2] = {0, 0};
@@ -325,12 +321,6 @@ namespace {
 
 #define XALLOC(ptr, elems) POOL_ALLOC(m->pool, ptr, (int64_t)(elems) * 4, m->stream, rc_)
 
-const ParamDesc* find_param(const vitx_engine* e, const std::string& name) {
-  for (const auto& p : e->table)
-    if (p.name == name) return &p;
-  return nullptr;
-}
-
 void crossvit_destroy(vitx_crossvit* m) {
   if (!m) return;
   (void)hipDeviceSynchronize();
@@ -390,21 +380,8 @@ int crossvit_create(const vitx_crossvit_config& cin, vitx_crossvit** out, std::s
   // parameter maps
   m->eng_maps.assign(m->eng.size(), {});
   m->head_maps.assign(m->eng.size(), {});
-  auto cpos = [&](const std::string& n) -> const ParamDesc* {
-    for (const auto& p : m->table) if (p.name == n) return &p;
-    return nullptr;
-  };
   auto add_map = [&](int ei, const std::string& cname, const std::string& ename, int64_t col0, int64_t width, bool head) -> bool {
-    const ParamDesc* cp = cpos(cname);
-    const ParamDesc* ep = find_param(m->eng[(size_t)ei], ename);
-    if (!cp || !ep) { err = "internal: parameter map " + cname + " -> " + ename; return false; }
-    XMap x;
-    x.eng = ei; x.coff = cp->aoff;
-    if (width < 0) { x.ldc = x.lde = x.width = cp->count; x.rows = 1; x.eoff = ep->aoff; }
-    else { x.rows = cp->shape[0]; x.width = width; x.ldc = width; x.lde = ep->shape[1]; x.eoff = ep->aoff + col0; }
-    (head ? m->head_maps : m->eng_maps)[(size_t)ei].push_back((int)m->maps.size());
-    m->maps.push_back(x);
-    return true;
+    return add_arena_map((head ? m->head_maps : m->eng_maps)[(size_t)ei], m->table, cname, m->eng[(size_t)ei]->table, ename, err, col0, width) == VITX_OK;
   };
   static const char* BR[2] = {"sm", "lg"};
   for (int br = 0; br < 2; ++br) {
@@ -470,22 +447,16 @@ void bind_streams(vitx_crossvit* m) {
 
 // composite arena -> every engine's arena (the encoders' to_q | to_kv become the column blocks of to_qkv)
 int push_params(vitx_crossvit* m, std::string& err) {
-  for (const XMap& x : m->maps) {
-    vitx_engine* e = m->eng[(size_t)x.eng];
-    HIPCHK(hipMemcpy2DAsync(e->params + x.eoff, (size_t)x.lde * 4, m->params + x.coff, (size_t)x.ldc * 4, (size_t)x.width * 4, (size_t)x.rows,
-                            hipMemcpyDeviceToDevice, m->stream));
-  }
+  int rc;
+  for (size_t ei = 0; ei < m->eng.size(); ++ei)
+    for (const auto* maps : {&m->eng_maps[ei], &m->head_maps[ei]})
+      if ((rc = copy_maps(m->params, m->eng[ei]->params, *maps, true, m->stream, err)) != VITX_OK) return rc;
   for (auto* e : m->eng) e->params_dirty = true;
   return VITX_OK;
 }
-int pull_grads(vitx_crossvit* m, const std::vector<int>& which, std::string& err) {
-  for (int i : which) {
-    const XMap& x = m->maps[(size_t)i];
-    vitx_engine* e = m->eng[(size_t)x.eng];
-    HIPCHK(hipMemcpy2DAsync(m->grads + x.coff, (size_t)x.ldc * 4, e->grads + x.eoff, (size_t)x.lde * 4, (size_t)x.width * 4, (size_t)x.rows,
-                            hipMemcpyDeviceToDevice, m->stream));
-  }
-  return VITX_OK;
+// one engine's gradients of one of its two lists -> the composite's arena
+int pull_grads(vitx_crossvit* m, int ei, const std::vector<std::vector<ArenaMap>>& lists, std::string& err) {
+  return copy_maps(m->grads, m->eng[(size_t)ei]->grads, lists[(size_t)ei], false, m->stream, err);
 }
 
 void launch_xattn_fwd(const float* q, const float* kv, float* o, float* lse, int b, int nk, int h, int dh, hipStream_t s) {
@@ -617,7 +588,7 @@ int crossvit_backward(vitx_crossvit* m, const float* dlogits_dev, float* dimg_de
   for (int br = 0; br < 2; ++br) {
     const int ei = br * D + D - 1;
     if ((rc = engine_head_backward(m->eng[(size_t)ei], dlogits_dev, m->G[br], err)) != VITX_OK) return rc;
-    if ((rc = pull_grads(m, m->head_maps[(size_t)ei], err)) != VITX_OK) return rc;   // before that engine's transformer backward clears its arena
+    if ((rc = pull_grads(m, ei, m->head_maps, err)) != VITX_OK) return rc;   // before that engine's transformer backward clears its arena
   }
   for (int i = D - 1; i >= 0; --i) {
     for (int k = c.cross_attn_depth - 1; k >= 0; --k)
@@ -637,7 +608,7 @@ int crossvit_backward(vitx_crossvit* m, const float* dlogits_dev, float* dimg_de
         // the fold-back writes (not adds) every pixel: the lg branch's goes to a buffer of its own, summed below (both embedders read img)
         if ((rc = engine_embed_backward(e, m->G[br], dimg_dev ? (br ? m->dimg_lg : dimg_dev) : nullptr, err)) != VITX_OK) return rc;
       }
-      if ((rc = pull_grads(m, m->eng_maps[(size_t)ei], err)) != VITX_OK) return rc;
+      if ((rc = pull_grads(m, ei, m->eng_maps, err)) != VITX_OK) return rc;
     }
   }
   if (dimg_dev) {
@@ -652,37 +623,17 @@ int crossvit_backward(vitx_crossvit* m, const float* dlogits_dev, float* dimg_de
 extern "C" {
 
 int32_t vitx_crossvit_param_table_size(const vitx_crossvit_config* cfg, int64_t* n_tensors, int64_t* n_elems) {
-  CAPI_TRY
   if (!cfg) return capi_fail(VITX_ERR_INVALID, "null argument");
-  std::vector<ParamDesc> t;
-  int64_t n = 0;
-  std::string e = crossvit_param_table(*cfg, t, &n, nullptr);
-  if (!e.empty()) return capi_fail(VITX_ERR_INVALID, e);
-  if (n_tensors) *n_tensors = (int64_t)t.size();
-  if (n_elems) *n_elems = n;
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_table_size(*cfg, n_tensors, n_elems, crossvit_param_table);
 }
 int32_t vitx_crossvit_param_table_entry(const vitx_crossvit_config* cfg, int64_t index, char* name, int32_t name_cap, int64_t shape[4], int32_t* rank,
                                         int64_t* offset_elems) {
-  CAPI_TRY
   if (!cfg) return capi_fail(VITX_ERR_INVALID, "null argument");
-  std::vector<ParamDesc> t;
-  std::string e = crossvit_param_table(*cfg, t, nullptr, nullptr);
-  if (!e.empty()) return capi_fail(VITX_ERR_INVALID, e);
-  return write_table_entry(t, index, name, name_cap, shape, rank, offset_elems);
-  CAPI_CATCH
+  return composite_table_entry(*cfg, index, name, name_cap, shape, rank, offset_elems, crossvit_param_table);
 }
 int32_t vitx_crossvit_create(const vitx_crossvit_config* cfg, vitx_crossvit_handle* out) {
-  CAPI_TRY
   if (!cfg || !out) return capi_fail(VITX_ERR_INVALID, "null argument");
-  std::string err;
-  vitx_crossvit* m = nullptr;
-  int rc = crossvit_create(*cfg, &m, err);
-  if (rc != VITX_OK) return capi_fail(rc, err);
-  *out = m;
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_create(*cfg, out, crossvit_create);
 }
 int32_t vitx_crossvit_destroy(vitx_crossvit_handle m) {
   CAPI_TRY
@@ -727,18 +678,9 @@ int32_t vitx_crossvit_backward_dev(vitx_crossvit_handle m, const float* dlogits_
   CAPI_CATCH
 }
 int32_t vitx_crossvit_backward(vitx_crossvit_handle m, const float* dlogits_host, float* dimg_host_or_null) {
-  CAPI_TRY
   if (!m || !dlogits_host) return capi_fail(VITX_ERR_INVALID, "null argument");
-  if (!m->have_fwd) return capi_fail(VITX_ERR_STATE, "backward requires a preceding forward");
-  CAPI_HIP(hipMemcpyAsync(m->dlogits, dlogits_host, (size_t)m->b * m->nc * 4, hipMemcpyHostToDevice, m->stream));
-  std::string err;
-  int rc = crossvit_backward(m, m->dlogits, dimg_host_or_null ? m->dimg : nullptr, err);
-  if (rc != VITX_OK) return capi_fail(rc, err);
-  if (dimg_host_or_null)
-    CAPI_HIP(hipMemcpyAsync(dimg_host_or_null, m->dimg, (size_t)m->b * m->H * m->W * 3 * 4, hipMemcpyDeviceToHost, m->stream));
-  CAPI_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_backward_host(m, dlogits_host, dimg_host_or_null, (int64_t)m->H * m->W * 3,
+                                 [&](float* dimg_dev, std::string& err) { return crossvit_backward(m, m->dlogits, dimg_dev, err); });
 }
 // "sm_tokens" / "lg_tokens": the final tokens [b, n, dim] (after the last cross layer); "sm_logits" / "lg_logits": the two heads
 int32_t vitx_crossvit_read(vitx_crossvit_handle m, const char* which, float* out_host, int64_t cap, int64_t* n_elems) {
@@ -754,11 +696,7 @@ int32_t vitx_crossvit_read(vitx_crossvit_handle m, const char* which, float* out
   else if (w == "sm_logits") { src = m->logit_br[0]; n = (int64_t)m->b * m->nc; }
   else if (w == "lg_logits") { src = m->logit_br[1]; n = (int64_t)m->b * m->nc; }
   else return capi_fail(VITX_ERR_INVALID, "unknown tensor name");
-  if (n_elems) *n_elems = n;
-  if (n > cap) return capi_fail(VITX_ERR_INVALID, "output buffer too small");
-  CAPI_HIP(hipMemcpyAsync(out_host, src, (size_t)n * 4, hipMemcpyDeviceToHost, m->stream));
-  CAPI_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
+  return composite_read_tail(src, n, out_host, cap, n_elems, m->stream);
   CAPI_CATCH
 }
 

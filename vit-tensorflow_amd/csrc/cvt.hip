@@ -12,8 +12,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
-#include <new>
 
 #include "composite.h"
 #include "conv_same.h"
@@ -24,16 +22,13 @@ constexpr int CV_STAGES = 3, CV_DIM_HEAD = 64;   // cvt.py:130: CvT never passes
 // what fused_attn = 0 means for at most 64 keys (attn_fewkey) and for 65 .. MANYKEY_MAX keys (attn_manykey): DESIGN.md section 22
 constexpr bool CV_FEWKEY_DEFAULT = true, CV_MANYKEY_DEFAULT = true;
 
-// a run of the composite's arena and where it lives in an engine's
-struct CvtMap { int64_t c, e, count; };
-
 struct CvtStage {
   int d = 0, ek = 0, es = 0, pk = 0, ks = 0, heads = 0, depth = 0, mult = 0;   // s{i}_emb_dim, _emb_kernel, _emb_stride, _proj_kernel, _kv_proj_stride, _heads, _depth, _mlp_mult
   int cin = 0, K = 0, Kp = 0, chunk = 1;                                       // input channels, k * k * cin, its row stride, images per im2col pass
   int Hin = 0, Win = 0, H = 0, W = 0, Hk = 0, Wk = 0;                          // the stage's input map, its own, and the kv map
   int64_t emb_w = -1, emb_b = -1, ln_g = -1, ln_b = -1;                        // arena offsets
   vitx_engine* eng = nullptr;
-  std::vector<CvtMap> maps;
+  std::vector<ArenaMap> maps;
   float *x_in = nullptr, *conv = nullptr, *mean = nullptr, *rstd = nullptr, *emb = nullptr, *out = nullptr;
 };
 
@@ -188,22 +183,14 @@ int cvt_maps(vitx_cvt* m, size_t si, std::string& err) {
       {"attn.to_out.kernel", "attn.to_out.kernel"}, {"attn.to_out.bias", "attn.to_out.bias"},
       {"ff.norm.g", "mlp.norm.gamma"}, {"ff.norm.b", "mlp.norm.beta"}, {"ff.fc1.kernel", "mlp.fc1.kernel"}, {"ff.fc1.bias", "mlp.fc1.bias"},
       {"ff.fc2.kernel", "mlp.fc2.kernel"}, {"ff.fc2.bias", "mlp.fc2.bias"}};
-  auto find = [](const std::vector<ParamDesc>& t, const std::string& n) -> const ParamDesc* {
-    for (const auto& p : t) if (p.name == n) return &p;
-    return nullptr;
-  };
-  for (int l = 0; l < S.depth; ++l) {
+  int rc = VITX_OK;
+  for (int l = 0; l < S.depth && rc == VITX_OK; ++l) {
     const std::string q = "cvt_layers." + std::to_string(si) + ".transformer." + std::to_string(l) + ".";
     const std::string eq = "transformer." + std::to_string(l) + ".";
-    for (const auto& pr : NAMES) {
-      const ParamDesc *cp = find(m->table, q + pr[0]), *ep = find(S.eng->table, eq + pr[1]);
-      if (!cp || !ep || cp->count != ep->count) { err = "internal: parameter map " + q + pr[0] + " -> " + eq + pr[1]; return VITX_ERR_INVALID; }
-      const int64_t span = round_up(cp->count, 4);
-      if (!S.maps.empty() && S.maps.back().c + S.maps.back().count == cp->aoff && S.maps.back().e + S.maps.back().count == ep->aoff) S.maps.back().count += span;
-      else S.maps.push_back({cp->aoff, ep->aoff, span});
-    }
+    for (const auto& pr : NAMES)
+      if ((rc = add_arena_map(S.maps, m->table, q + pr[0], S.eng->table, eq + pr[1], err)) != VITX_OK) break;
   }
-  return VITX_OK;
+  return rc;
 }
 
 int cvt_create(const vitx_cvt_config& cin, vitx_cvt** out, std::string& err) {
@@ -259,31 +246,15 @@ int cvt_create(const vitx_cvt_config& cin, vitx_cvt** out, std::string& err) {
   return VITX_OK;
 }
 
-int copy_maps(vitx_cvt* m, const CvtStage& S, bool to_engine, std::string& err) {
-  for (const CvtMap& t : S.maps) {
-    float* cp = (to_engine ? m->params : m->grads) + t.c;
-    float* ep = (to_engine ? S.eng->params : S.eng->grads) + t.e;
-    HIPCHK(hipMemcpyAsync(to_engine ? ep : cp, to_engine ? cp : ep, (size_t)t.count * 4, hipMemcpyDeviceToDevice, m->stream));
-  }
-  return VITX_OK;
-}
 int push_params(vitx_cvt* m, std::string& err) {
   int rc;
   for (CvtStage& S : m->st) {
     if (!S.eng) continue;
-    if ((rc = copy_maps(m, S, true, err)) != VITX_OK) return rc;
+    if ((rc = copy_maps(m->params, S.eng->params, S.maps, true, m->stream, err)) != VITX_OK) return rc;
     S.eng->params_dirty = true;
   }
   return VITX_OK;
 }
-
-// a composite launch booked on the first engine's profiler (a handle without blocks has none and profiles nothing)
-struct CvtProf {
-  alignas(CompositeProf) char buf[sizeof(CompositeProf)];
-  CompositeProf* p = nullptr;
-  CvtProf(vitx_cvt* m, const char* name) { if (m->prof_eng) p = new (buf) CompositeProf(m->prof_eng, name); }
-  ~CvtProf() { if (p) p->~CompositeProf(); }
-};
 
 int cvt_forward(vitx_cvt* m, const float* img_dev, int b, int training, std::string& err) {
   const vitx_cvt_config& c = m->cfg;
@@ -302,12 +273,12 @@ int cvt_forward(vitx_cvt* m, const float* img_dev, int b, int training, std::str
     // Conv2D 'SAME' with bias (cvt.py:187) in image chunks, then the channel LayerNorm (:188)
     for (int b0 = 0; b0 < b; b0 += S.chunk) {
       const int nb = std::min(S.chunk, b - b0);
-      { CvtProf pr(m, "cvt_im2col"); launch_cct_im2col(x_in + b0 * in_img, m->rows, nb, S.Hin, S.Win, S.cin, S.ek, S.es, S.Kp, s); }
-      CvtProf pr(m, "cvt_conv_gemm");
+      { CompositeProf pr(m->prof_eng, "cvt_im2col"); launch_cct_im2col(x_in + b0 * in_img, m->rows, nb, S.Hin, S.Win, S.cin, S.ek, S.es, S.Kp, s); }
+      CompositeProf pr(m->prof_eng, "cvt_conv_gemm");
       dense_fwd(m->rows, S.Kp, P + S.emb_w, P + S.emb_b, S.conv + b0 * out_img, nb * px, S.d, S.K, s, m->x3);
     }
     {
-      CvtProf pr(m, "cvt_embed_norm");
+      CompositeProf pr(m->prof_eng, "cvt_embed_norm");
       launch_layernorm_fwd(S.conv, S.d, P + S.ln_g, P + S.ln_b, S.emb, 0, S.d, S.mean, S.rstd, b * px, S.d, c.ln_eps, s);
     }
     if (!S.eng) continue;
@@ -317,7 +288,7 @@ int cvt_forward(vitx_cvt* m, const float* img_dev, int b, int training, std::str
   }
   // GlobalAvgPool2D + Dense (:195-198)
   const CvtStage& last = m->st.back();
-  CvtProf pr(m, "cvt_head");
+  CompositeProf pr(m->prof_eng, "cvt_head");
   launch_mean_pool(last.out, b, last.H * last.W, last.d, m->pooled, s);
   dense_fwd(m->pooled, last.d, P + m->fc_w, P + m->fc_b, m->logits, b, m->nc, last.d, s);
   m->have_fwd = true;
@@ -343,7 +314,7 @@ int cvt_backward(vitx_cvt* m, const float* dlogits_dev, float* dimg_dev, std::st
   {
     const CvtStage& last = m->st.back();
     const int d = last.d;
-    CvtProf pr(m, "cvt_head");
+    CompositeProf pr(m->prof_eng, "cvt_head");
     dense_dw(m->pooled, d, dlogits_dev, G + m->fc_w, b, m->nc, d, s);
     launch_colsum(dlogits_dev, 0, m->nc, b, m->nc, m->ws, G + m->fc_b, s);
     dense_dx(dlogits_dev, P + m->fc_w, m->dpooled, b, m->nc, d, s);
@@ -357,10 +328,10 @@ int cvt_backward(vitx_cvt* m, const float* dlogits_dev, float* dimg_dev, std::st
     if (S.eng) {
       S.eng->stream = s;
       if ((rc = engine_transformer_backward(S.eng, g, g, err)) != VITX_OK) return rc;
-      if ((rc = copy_maps(m, S, false, err)) != VITX_OK) return rc;
+      if ((rc = copy_maps(m->grads, S.eng->grads, S.maps, false, s, err)) != VITX_OK) return rc;
     }
     {   // g = d(emb) -> g2 = d(conv)
-      CvtProf pr(m, "cvt_embed_norm");
+      CompositeProf pr(m->prof_eng, "cvt_embed_norm");
       launch_layernorm_bwd(g, 0, S.d, S.conv, S.d, S.mean, S.rstd, P + S.ln_g, nullptr, 0, g2, S.d, nullptr, 0, m->ws, G + S.ln_g, G + S.ln_b, nullptr, rows_all,
                            S.d, s);
       launch_colsum(g2, 0, S.d, rows_all, S.d, m->ws, G + S.emb_b, s);
@@ -372,16 +343,16 @@ int cvt_backward(vitx_cvt* m, const float* dlogits_dev, float* dimg_dev, std::st
       const int nb = std::min(S.chunk, b - b0);
       const int rows = nb * px;
       const float* dy = g2 + b0 * out_img;
-      { CvtProf pr(m, "cvt_im2col"); launch_cct_im2col(x_in + b0 * in_img, m->rows, nb, S.Hin, S.Win, S.cin, S.ek, S.es, S.Kp, s); }
+      { CompositeProf pr(m->prof_eng, "cvt_im2col"); launch_cct_im2col(x_in + b0 * in_img, m->rows, nb, S.Hin, S.Win, S.cin, S.ek, S.es, S.Kp, s); }
       {
-        CvtProf pr(m, "cvt_conv_gemm");
+        CompositeProf pr(m->prof_eng, "cvt_conv_gemm");
         conv_wgrad(m->rows, S.Kp, dy, m->gw_part, m->gw_slices, rows, S.d, m->x3, s);
         const int64_t nw = (int64_t)S.K * S.d;
         hipLaunchKernelGGL(conv_accum_kernel, dim3(grid256(nw)), dim3(256), 0, s, G + S.emb_w, (const float*)m->gw_part, nw, b0 == 0 ? 1 : 0);
         if (want_dx) dense_dx(dy, P + S.emb_w, m->drows, rows, S.d, S.K, s, m->x3);
       }
       if (!want_dx) continue;
-      CvtProf pr(m, "cvt_col2im");
+      CompositeProf pr(m->prof_eng, "cvt_col2im");
       launch_extract_patches_bwd(m->drows, dxin + b0 * in_img, nb, S.Hin, S.Win, S.cin, S.ek, S.es, s);
     }
     // g now holds d(the previous stage's output); g2 is free again
@@ -400,37 +371,17 @@ std::vector<vitx_engine*> cvt_engines(vitx_cvt* m) {
 extern "C" {
 
 int32_t vitx_cvt_param_table_size(const vitx_cvt_config* cfg, int64_t* n_tensors, int64_t* n_elems) {
-  CAPI_TRY
   if (!cfg) return capi_fail(VITX_ERR_INVALID, "null argument");
-  std::vector<ParamDesc> t;
-  int64_t n = 0;
-  std::string e = cvt_param_table(*cfg, t, &n, nullptr);
-  if (!e.empty()) return capi_fail(VITX_ERR_INVALID, e);
-  if (n_tensors) *n_tensors = (int64_t)t.size();
-  if (n_elems) *n_elems = n;
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_table_size(*cfg, n_tensors, n_elems, cvt_param_table);
 }
 int32_t vitx_cvt_param_table_entry(const vitx_cvt_config* cfg, int64_t index, char* name, int32_t name_cap, int64_t shape[4], int32_t* rank,
                                    int64_t* offset_elems) {
-  CAPI_TRY
   if (!cfg) return capi_fail(VITX_ERR_INVALID, "null argument");
-  std::vector<ParamDesc> t;
-  std::string e = cvt_param_table(*cfg, t, nullptr, nullptr);
-  if (!e.empty()) return capi_fail(VITX_ERR_INVALID, e);
-  return write_table_entry(t, index, name, name_cap, shape, rank, offset_elems);
-  CAPI_CATCH
+  return composite_table_entry(*cfg, index, name, name_cap, shape, rank, offset_elems, cvt_param_table);
 }
 int32_t vitx_cvt_create(const vitx_cvt_config* cfg, vitx_cvt_handle* out) {
-  CAPI_TRY
   if (!cfg || !out) return capi_fail(VITX_ERR_INVALID, "null argument");
-  std::string err;
-  vitx_cvt* m = nullptr;
-  int rc = cvt_create(*cfg, &m, err);
-  if (rc != VITX_OK) return capi_fail(rc, err);
-  *out = m;
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_create(*cfg, out, cvt_create);
 }
 int32_t vitx_cvt_destroy(vitx_cvt_handle m) {
   CAPI_TRY
@@ -453,17 +404,9 @@ int32_t vitx_cvt_forward_dev(vitx_cvt_handle m, const float* img_dev, int32_t b,
   CAPI_CATCH
 }
 int32_t vitx_cvt_forward(vitx_cvt_handle m, const float* img_host, int32_t b, int32_t training, float* logits_host) {
-  CAPI_TRY
   if (!m || !img_host || !logits_host) return capi_fail(VITX_ERR_INVALID, "null argument");
-  if (b <= 0 || b > m->cfg.max_batch) return capi_fail(VITX_ERR_INVALID, "batch must be in [1, max_batch]");
-  CAPI_HIP(hipMemcpyAsync(m->img, img_host, (size_t)b * m->cfg.image_h * m->cfg.image_w * 3 * 4, hipMemcpyHostToDevice, m->stream));
-  std::string err;
-  int rc = cvt_forward(m, m->img, b, training, err);
-  if (rc != VITX_OK) return capi_fail(rc, err);
-  CAPI_HIP(hipMemcpyAsync(logits_host, m->logits, (size_t)b * m->nc * 4, hipMemcpyDeviceToHost, m->stream));
-  CAPI_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_forward_host(m, img_host, (int64_t)m->cfg.image_h * m->cfg.image_w * 3, b, logits_host,
+                                [&](std::string& err) { return cvt_forward(m, m->img, b, training, err); });
 }
 int32_t vitx_cvt_backward_dev(vitx_cvt_handle m, const float* dlogits_dev, float* dimg_dev_or_null) {
   CAPI_TRY
@@ -475,56 +418,17 @@ int32_t vitx_cvt_backward_dev(vitx_cvt_handle m, const float* dlogits_dev, float
   CAPI_CATCH
 }
 int32_t vitx_cvt_backward(vitx_cvt_handle m, const float* dlogits_host, float* dimg_host_or_null) {
-  CAPI_TRY
   if (!m || !dlogits_host) return capi_fail(VITX_ERR_INVALID, "null argument");
-  if (!m->have_fwd) return capi_fail(VITX_ERR_STATE, "backward requires a preceding forward");
-  CAPI_HIP(hipMemcpyAsync(m->dlogits, dlogits_host, (size_t)m->b * m->nc * 4, hipMemcpyHostToDevice, m->stream));
-  std::string err;
-  int rc = cvt_backward(m, m->dlogits, dimg_host_or_null ? m->dimg : nullptr, err);
-  if (rc != VITX_OK) return capi_fail(rc, err);
-  if (dimg_host_or_null)
-    CAPI_HIP(hipMemcpyAsync(dimg_host_or_null, m->dimg, (size_t)m->b * m->cfg.image_h * m->cfg.image_w * 3 * 4, hipMemcpyDeviceToHost, m->stream));
-  CAPI_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_backward_host(m, dlogits_host, dimg_host_or_null, (int64_t)m->cfg.image_h * m->cfg.image_w * 3,
+                                 [&](float* dimg_dev, std::string& err) { return cvt_backward(m, m->dlogits, dimg_dev, err); });
 }
-
 int32_t vitx_cvt_profile_begin(vitx_cvt_handle m) {
-  CAPI_TRY
   if (!m) return capi_fail(VITX_ERR_INVALID, "null handle");
-  const std::vector<vitx_engine*> engs = cvt_engines(m);
-  for (size_t i = 0; i < engs.size(); ++i) {
-    const int rc = vitx_profile_begin(engs[i]);
-    if (rc == VITX_OK) continue;
-    for (size_t j = 0; j < i; ++j) (void)vitx_profile_end(engs[j], nullptr, 0, nullptr);   // leave no engine profiling behind a failure
-    return rc;
-  }
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_profile_begin(cvt_engines(m));
 }
-// the engines each keep their own classes: the same class of several engines is summed
 int32_t vitx_cvt_profile_end(vitx_cvt_handle m, vitx_kernel_stat* out, int32_t cap, int32_t* n_out) {
-  CAPI_TRY
   if (!m) return capi_fail(VITX_ERR_INVALID, "null handle");
-  std::vector<vitx_kernel_stat> all, one(256);
-  int first_err = VITX_OK;
-  std::map<std::string, size_t> at;
-  for (vitx_engine* eng : cvt_engines(m)) {
-    int32_t k = 0;
-    const int rc = vitx_profile_end(eng, one.data(), (int32_t)one.size(), &k);
-    if (rc != VITX_OK) { if (first_err == VITX_OK) first_err = rc; continue; }   // (the other engines still stop profiling and release their events)
-    for (int32_t j = 0; j < std::min<int32_t>(k, (int32_t)one.size()); ++j) {
-      const auto it = at.find(one[(size_t)j].name);
-      if (it == at.end()) { at[one[(size_t)j].name] = all.size(); all.push_back(one[(size_t)j]); continue; }
-      vitx_kernel_stat& t = all[it->second];
-      t.launches += one[(size_t)j].launches; t.total_ms += one[(size_t)j].total_ms; t.flops += one[(size_t)j].flops; t.bytes += one[(size_t)j].bytes;
-    }
-  }
-  if (first_err != VITX_OK) return first_err;
-  for (size_t j = 0; j < all.size() && out && (int32_t)j < cap; ++j) out[j] = all[j];
-  if (n_out) *n_out = (int32_t)all.size();
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_profile_end(cvt_engines(m), out, cap, n_out);
 }
 int32_t vitx_cvt_read(vitx_cvt_handle m, const char* which, float* out_host, int64_t cap, int64_t* n_elems) {
   CAPI_TRY
@@ -565,11 +469,7 @@ int32_t vitx_cvt_read(vitx_cvt_handle m, const char* which, float* out_host, int
     src = m->tap;
   }
   else return capi_fail(VITX_ERR_INVALID, "unknown tensor name");
-  if (n_elems) *n_elems = n;
-  if (n > cap) return capi_fail(VITX_ERR_INVALID, "output buffer too small");
-  CAPI_HIP(hipMemcpyAsync(out_host, src, (size_t)n * 4, hipMemcpyDeviceToHost, m->stream));
-  CAPI_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
+  return composite_read_tail(src, n, out_host, cap, n_elems, m->stream);
   CAPI_CATCH
 }
 

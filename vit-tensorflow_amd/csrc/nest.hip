@@ -10,7 +10,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 
 #include "composite.h"
 #include "conv_same.h"
@@ -26,8 +25,7 @@ struct NestLevel {
   int dn = 0, K = 0, Kp = 0, chunk = 1;                 // aggregation (not at the last level): filters, 9 * d, its row stride, images per pass
   int64_t pos = -1, conv_w = -1, conv_b = -1, ag_g = -1, ag_b = -1;   // arena offsets
   vitx_engine* eng = nullptr;                           // depth > 0
-  std::vector<std::pair<int64_t, int64_t>> maps;        // (composite arena offset, engine arena offset) per engine tensor
-  std::vector<int64_t> map_count;
+  std::vector<ArenaMap> maps;                           // the level's block tensors -> the engine's
   float *x_in = nullptr, *out = nullptr;                // [B, f, f, d]: the level's input map (embedded / the pooled map below) and its output
   float *conv = nullptr, *ln = nullptr, *pooled = nullptr, *mean = nullptr, *rstd = nullptr;   // [B, f, f, dn] x 2, [B, f/2, f/2, dn], [B f f] x 2
 };
@@ -187,10 +185,6 @@ int nest_create(const vitx_nest_config& cin, vitx_nest** out, std::string& err) 
                                    {"attn.to_out.kernel", "attn.to_out.kernel"}, {"attn.to_out.bias", "attn.to_out.bias"},
                                    {"ff.norm.g", "mlp.norm.gamma"}, {"ff.norm.b", "mlp.norm.beta"}, {"ff.fc1.kernel", "mlp.fc1.kernel"},
                                    {"ff.fc1.bias", "mlp.fc1.bias"}, {"ff.fc2.kernel", "mlp.fc2.kernel"}, {"ff.fc2.bias", "mlp.fc2.bias"}};
-  auto find = [](const std::vector<ParamDesc>& t, const std::string& n) -> const ParamDesc* {
-    for (const auto& p : t) if (p.name == n) return &p;
-    return nullptr;
-  };
   for (size_t i = 0; i < m->lv.size(); ++i) {
     NestLevel& L = m->lv[i];
     if (L.depth == 0) continue;
@@ -199,13 +193,9 @@ int nest_create(const vitx_nest_config& cin, vitx_nest** out, std::string& err) 
     L.eng->small_attn = c.small_attn > 0 || (c.small_attn == 0 && c.compute == VITX_COMPUTE_BF16);
     if (!m->prof_eng) { m->prof_eng = L.eng; m->stream = L.eng->stream; }
     for (int l = 0; l < L.depth; ++l)
-      for (const auto& pr : PAIRS) {
-        const ParamDesc* cp = find(m->table, "nest_layers." + std::to_string(i) + ".transformer." + std::to_string(l) + "." + pr[0]);
-        const ParamDesc* ep = find(L.eng->table, "transformer." + std::to_string(l) + "." + pr[1]);
-        if (!cp || !ep || cp->count != ep->count) { err = std::string("internal: parameter map ") + pr[0] + " -> " + pr[1]; return fail(VITX_ERR_INVALID); }
-        L.maps.push_back({cp->aoff, ep->aoff});
-        L.map_count.push_back(cp->count);
-      }
+      for (const auto& pr : PAIRS)
+        if ((rc = add_arena_map(L.maps, m->table, "nest_layers." + std::to_string(i) + ".transformer." + std::to_string(l) + "." + pr[0], L.eng->table,
+                                "transformer." + std::to_string(l) + "." + pr[1], err)) != VITX_OK) return fail(rc);
   }
   if (!m->stream) {   // no level has blocks: the composite runs alone
     int ndev = 0;
@@ -253,27 +243,19 @@ int nest_create(const vitx_nest_config& cin, vitx_nest** out, std::string& err) 
 }
 
 int push_params(vitx_nest* m, std::string& err) {
+  int rc;
   for (NestLevel& L : m->lv) {
     if (!L.eng) continue;
-    for (size_t i = 0; i < L.maps.size(); ++i)
-      HIPCHK(hipMemcpyAsync(L.eng->params + L.maps[i].second, m->params + L.maps[i].first, (size_t)L.map_count[i] * 4, hipMemcpyDeviceToDevice, m->stream));
+    if ((rc = copy_maps(m->params, L.eng->params, L.maps, true, m->stream, err)) != VITX_OK) return rc;
     L.eng->params_dirty = true;
   }
   return VITX_OK;
 }
-int pull_grads(vitx_nest* m, NestLevel& L, std::string& err) {
-  for (size_t i = 0; i < L.maps.size(); ++i)
-    HIPCHK(hipMemcpyAsync(m->grads + L.maps[i].first, L.eng->grads + L.maps[i].second, (size_t)L.map_count[i] * 4, hipMemcpyDeviceToDevice, m->stream));
-  return VITX_OK;
+std::vector<vitx_engine*> nest_engines(vitx_nest* m) {
+  std::vector<vitx_engine*> v;
+  for (NestLevel& L : m->lv) if (L.eng) v.push_back(L.eng);
+  return v;
 }
-
-// a composite launch booked on the first engine's profiler (a handle without blocks has none and profiles nothing)
-struct NestProf {
-  alignas(CompositeProf) char buf[sizeof(CompositeProf)];
-  CompositeProf* p = nullptr;
-  NestProf(vitx_nest* m, const char* name) { if (m->prof_eng) p = new (buf) CompositeProf(m->prof_eng, name); }
-  ~NestProf() { if (p) p->~CompositeProf(); }
-};
 
 int nest_forward(vitx_nest* m, const float* img_dev, int b, std::string& err) {
   const vitx_nest_config& c = m->cfg;
@@ -284,14 +266,14 @@ int nest_forward(vitx_nest* m, const float* img_dev, int b, std::string& err) {
   m->b = b;
   const int n = m->n, hb = m->hb, f0 = m->fmap;
   {   // patch embedding (nest.py:178-181): the (p1 p2 c) feature order of launch_unfold is the reference's Rearrange
-    NestProf pr(m, "nest_embed");
+    CompositeProf pr(m->prof_eng, "nest_embed");
     launch_unfold(img_dev, m->patches, 0, b, c.image_size, c.image_size, 3, c.patch_size, c.patch_size, m->pd, s);
     dense_fwd(m->patches, m->pd, P + m->emb_w, P + m->emb_b, m->lv[0].x_in, b * f0 * f0, c.dim, m->pd, s, m->x3);
   }
   for (size_t i = 0; i < m->lv.size(); ++i) {
     NestLevel& L = m->lv[i];
     const int nseq = b * L.nb * L.nb;
-    { NestProf pr(m, "nest_blocks"); launch_nest_to_blocks(L.x_in, P + L.pos, m->tok_a, b, L.nb, hb, hb, L.d, s); }   // :209 and :140-142
+    { CompositeProf pr(m->prof_eng, "nest_blocks"); launch_nest_to_blocks(L.x_in, P + L.pos, m->tok_a, b, L.nb, hb, hb, L.d, s); }   // :209 and :140-142
     const float* tok = m->tok_a;
     if (L.eng) {
       L.eng->stream = s;
@@ -299,23 +281,23 @@ int nest_forward(vitx_nest* m, const float* img_dev, int b, std::string& err) {
       if ((rc = engine_transformer_forward(L.eng, m->tok_a, nseq, n, 0, 0, m->tok_b, err)) != VITX_OK) return rc;   // :144-146
       tok = m->tok_b;
     }
-    { NestProf pr(m, "nest_blocks"); launch_nest_from_blocks(tok, L.out, b, L.nb, hb, hb, L.d, s); }                  // :211
+    { CompositeProf pr(m->prof_eng, "nest_blocks"); launch_nest_from_blocks(tok, L.out, b, L.nb, hb, hb, L.d, s); }                  // :211
     if (!L.dn) continue;
     // Aggregate (:111-123): conv in image chunks, LayerNorm, max-pool over the whole batch
     const int64_t in_img = (int64_t)L.f * L.f * L.d, out_img = (int64_t)L.f * L.f * L.dn;
     for (int b0 = 0; b0 < b; b0 += L.chunk) {
       const int nb = std::min(L.chunk, b - b0);
-      { NestProf pr(m, "nest_im2col"); launch_cct_im2col(L.out + b0 * in_img, m->rows, nb, L.f, L.f, L.d, 3, 1, L.Kp, s); }
-      NestProf pr(m, "nest_conv_gemm");
+      { CompositeProf pr(m->prof_eng, "nest_im2col"); launch_cct_im2col(L.out + b0 * in_img, m->rows, nb, L.f, L.f, L.d, 3, 1, L.Kp, s); }
+      CompositeProf pr(m->prof_eng, "nest_conv_gemm");
       dense_fwd(m->rows, L.Kp, P + L.conv_w, P + L.conv_b, L.conv + b0 * out_img, nb * L.f * L.f, L.dn, L.K, s, m->x3);
     }
     launch_layernorm_fwd(L.conv, L.dn, P + L.ag_g, P + L.ag_b, L.ln, 0, L.dn, L.mean, L.rstd, b * L.f * L.f, L.dn, c.ln_eps, s);
-    NestProf pr(m, "nest_maxpool_fwd");
+    CompositeProf pr(m->prof_eng, "nest_maxpool_fwd");
     launch_nest_maxpool_fwd(L.ln, L.pooled, b, L.f, L.f, L.dn, 3, 2, s);
   }
   // mlp_head (:196-200)
   const NestLevel& last = m->lv.back();
-  NestProf pr(m, "nest_head");
+  CompositeProf pr(m->prof_eng, "nest_head");
   launch_layernorm_fwd(last.out, last.d, P + m->head_g, P + m->head_b, m->xn, 0, last.d, m->mean, m->rstd, b * last.f * last.f, last.d, c.ln_eps, s);
   launch_mean_pool(m->xn, b, last.f * last.f, last.d, m->pooled, s);
   dense_fwd(m->pooled, last.d, P + m->fc_w, P + m->fc_b, m->logits, b, m->nc, last.d, s);
@@ -336,7 +318,7 @@ int nest_backward(vitx_nest* m, const float* dlogits_dev, float* dimg_dev, std::
   {
     const NestLevel& last = m->lv.back();
     const int ntok = last.f * last.f, d = last.d;
-    NestProf pr(m, "nest_head");
+    CompositeProf pr(m->prof_eng, "nest_head");
     dense_dw(m->pooled, d, dlogits_dev, G + m->fc_w, b, m->nc, d, s);
     launch_colsum(dlogits_dev, 0, m->nc, b, m->nc, m->ws, G + m->fc_b, s);
     dense_dx(dlogits_dev, P + m->fc_w, m->dpooled, b, m->nc, d, s);
@@ -349,23 +331,23 @@ int nest_backward(vitx_nest* m, const float* dlogits_dev, float* dimg_dev, std::
     const int nseq = b * L.nb * L.nb;
     const int a1 = (cur + 1) % 3, a2 = (cur + 2) % 3;
     // the partition's VJP is its inverse map and the other way round
-    { NestProf pr(m, "nest_blocks"); launch_nest_to_blocks(m->g[cur], nullptr, m->g[a1], b, L.nb, hb, hb, L.d, s); }
+    { CompositeProf pr(m->prof_eng, "nest_blocks"); launch_nest_to_blocks(m->g[cur], nullptr, m->g[a1], b, L.nb, hb, hb, L.d, s); }
     const float* dtok = m->g[a1];
     if (L.eng) {
       L.eng->stream = s;
       int rc;
       if ((rc = engine_transformer_backward(L.eng, m->g[a1], m->g[a2], err)) != VITX_OK) return rc;
-      if ((rc = pull_grads(m, L, err)) != VITX_OK) return rc;
+      if ((rc = copy_maps(m->grads, L.eng->grads, L.maps, false, m->stream, err)) != VITX_OK) return rc;
       dtok = m->g[a2];
     }
     float* dxin = const_cast<float*>(dtok) == m->g[a1] ? m->g[a2] : m->g[a1];
     {
-      NestProf pr(m, "nest_blocks");
+      CompositeProf pr(m->prof_eng, "nest_blocks");
       launch_nest_dpos(dtok, m->dpos_part, G + L.pos, nseq, n, L.d, s);
       launch_nest_from_blocks(dtok, dxin, b, L.nb, hb, hb, L.d, s);
     }
     if (i == 0) {   // patch embedding
-      NestProf pr(m, "nest_embed");
+      CompositeProf pr(m->prof_eng, "nest_embed");
       const int rows = b * f0 * f0;
       dense_dw(m->patches, m->pd, dxin, G + m->emb_w, rows, c.dim, m->pd, s, m->x3);
       launch_colsum(dxin, 0, c.dim, rows, c.dim, m->ws, G + m->emb_b, s);
@@ -380,7 +362,7 @@ int nest_backward(vitx_nest* m, const float* dlogits_dev, float* dimg_dev, std::
     const int px = A.f * A.f;
     float* dln = m->g[cur];                                      // (d(level output) has been consumed)
     float* dconv = const_cast<float*>(dtok);                     // (so has d(tokens))
-    { NestProf pr(m, "nest_maxpool_bwd"); launch_nest_maxpool_bwd(A.ln, dxin, dln, b, A.f, A.f, A.dn, 3, 2, s); }
+    { CompositeProf pr(m->prof_eng, "nest_maxpool_bwd"); launch_nest_maxpool_bwd(A.ln, dxin, dln, b, A.f, A.f, A.dn, 3, 2, s); }
     launch_layernorm_bwd(dln, 0, A.dn, A.conv, A.dn, A.mean, A.rstd, P + A.ag_g, nullptr, 0, dconv, A.dn, nullptr, 0, m->ws, G + A.ag_g, G + A.ag_b, nullptr,
                          b * px, A.dn, s);
     launch_colsum(dconv, 0, A.dn, b * px, A.dn, m->ws, G + A.conv_b, s);
@@ -390,15 +372,15 @@ int nest_backward(vitx_nest* m, const float* dlogits_dev, float* dimg_dev, std::
       const int nb = std::min(A.chunk, b - b0);
       const int rows = nb * px;
       const float* dy = dconv + b0 * out_img;
-      { NestProf pr(m, "nest_im2col"); launch_cct_im2col(A.out + b0 * in_img, m->rows, nb, A.f, A.f, A.d, 3, 1, A.Kp, s); }
+      { CompositeProf pr(m->prof_eng, "nest_im2col"); launch_cct_im2col(A.out + b0 * in_img, m->rows, nb, A.f, A.f, A.d, 3, 1, A.Kp, s); }
       {
-        NestProf pr(m, "nest_conv_gemm");
+        CompositeProf pr(m->prof_eng, "nest_conv_gemm");
         conv_wgrad(m->rows, A.Kp, dy, m->gw_part, m->gw_slices, rows, A.dn, m->x3, s);
         const int64_t nw = (int64_t)A.K * A.dn;
         hipLaunchKernelGGL(conv_accum_kernel, dim3(grid256(nw)), dim3(256), 0, s, G + A.conv_w, (const float*)m->gw_part, nw, b0 == 0 ? 1 : 0);
         dense_dx(dy, P + A.conv_w, m->drows, rows, A.dn, A.K, s, m->x3);
       }
-      NestProf pr(m, "nest_col2im");
+      CompositeProf pr(m->prof_eng, "nest_col2im");
       launch_extract_patches_bwd(m->drows, dout + b0 * in_img, nb, A.f, A.f, A.d, 3, 1, s);
     }
     cur = (int)(dout == m->g[0] ? 0 : dout == m->g[1] ? 1 : 2);
@@ -411,37 +393,17 @@ int nest_backward(vitx_nest* m, const float* dlogits_dev, float* dimg_dev, std::
 extern "C" {
 
 int32_t vitx_nest_param_table_size(const vitx_nest_config* cfg, int64_t* n_tensors, int64_t* n_elems) {
-  CAPI_TRY
   if (!cfg) return capi_fail(VITX_ERR_INVALID, "null argument");
-  std::vector<ParamDesc> t;
-  int64_t n = 0;
-  std::string e = nest_param_table(*cfg, t, &n, nullptr);
-  if (!e.empty()) return capi_fail(VITX_ERR_INVALID, e);
-  if (n_tensors) *n_tensors = (int64_t)t.size();
-  if (n_elems) *n_elems = n;
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_table_size(*cfg, n_tensors, n_elems, nest_param_table);
 }
 int32_t vitx_nest_param_table_entry(const vitx_nest_config* cfg, int64_t index, char* name, int32_t name_cap, int64_t shape[4], int32_t* rank,
                                     int64_t* offset_elems) {
-  CAPI_TRY
   if (!cfg) return capi_fail(VITX_ERR_INVALID, "null argument");
-  std::vector<ParamDesc> t;
-  std::string e = nest_param_table(*cfg, t, nullptr, nullptr);
-  if (!e.empty()) return capi_fail(VITX_ERR_INVALID, e);
-  return write_table_entry(t, index, name, name_cap, shape, rank, offset_elems);
-  CAPI_CATCH
+  return composite_table_entry(*cfg, index, name, name_cap, shape, rank, offset_elems, nest_param_table);
 }
 int32_t vitx_nest_create(const vitx_nest_config* cfg, vitx_nest_handle* out) {
-  CAPI_TRY
   if (!cfg || !out) return capi_fail(VITX_ERR_INVALID, "null argument");
-  std::string err;
-  vitx_nest* m = nullptr;
-  int rc = nest_create(*cfg, &m, err);
-  if (rc != VITX_OK) return capi_fail(rc, err);
-  *out = m;
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_create(*cfg, out, nest_create);
 }
 int32_t vitx_nest_destroy(vitx_nest_handle m) {
   CAPI_TRY
@@ -462,17 +424,9 @@ int32_t vitx_nest_forward_dev(vitx_nest_handle m, const float* img_dev, int32_t 
   CAPI_CATCH
 }
 int32_t vitx_nest_forward(vitx_nest_handle m, const float* img_host, int32_t b, float* logits_host) {
-  CAPI_TRY
   if (!m || !img_host || !logits_host) return capi_fail(VITX_ERR_INVALID, "null argument");
-  if (b <= 0 || b > m->cfg.max_batch) return capi_fail(VITX_ERR_INVALID, "batch must be in [1, max_batch]");
-  CAPI_HIP(hipMemcpyAsync(m->img, img_host, (size_t)b * m->cfg.image_size * m->cfg.image_size * 3 * 4, hipMemcpyHostToDevice, m->stream));
-  std::string err;
-  int rc = nest_forward(m, m->img, b, err);
-  if (rc != VITX_OK) return capi_fail(rc, err);
-  CAPI_HIP(hipMemcpyAsync(logits_host, m->logits, (size_t)b * m->nc * 4, hipMemcpyDeviceToHost, m->stream));
-  CAPI_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_forward_host(m, img_host, (int64_t)m->cfg.image_size * m->cfg.image_size * 3, b, logits_host,
+                                [&](std::string& err) { return nest_forward(m, m->img, b, err); });
 }
 int32_t vitx_nest_backward_dev(vitx_nest_handle m, const float* dlogits_dev, float* dimg_dev_or_null) {
   CAPI_TRY
@@ -484,57 +438,17 @@ int32_t vitx_nest_backward_dev(vitx_nest_handle m, const float* dlogits_dev, flo
   CAPI_CATCH
 }
 int32_t vitx_nest_backward(vitx_nest_handle m, const float* dlogits_host, float* dimg_host_or_null) {
-  CAPI_TRY
   if (!m || !dlogits_host) return capi_fail(VITX_ERR_INVALID, "null argument");
-  if (!m->have_fwd) return capi_fail(VITX_ERR_STATE, "backward requires a preceding forward");
-  CAPI_HIP(hipMemcpyAsync(m->dlogits, dlogits_host, (size_t)m->b * m->nc * 4, hipMemcpyHostToDevice, m->stream));
-  std::string err;
-  int rc = nest_backward(m, m->dlogits, dimg_host_or_null ? m->dimg : nullptr, err);
-  if (rc != VITX_OK) return capi_fail(rc, err);
-  if (dimg_host_or_null)
-    CAPI_HIP(hipMemcpyAsync(dimg_host_or_null, m->dimg, (size_t)m->b * m->cfg.image_size * m->cfg.image_size * 3 * 4, hipMemcpyDeviceToHost, m->stream));
-  CAPI_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_backward_host(m, dlogits_host, dimg_host_or_null, (int64_t)m->cfg.image_size * m->cfg.image_size * 3,
+                                 [&](float* dimg_dev, std::string& err) { return nest_backward(m, m->dlogits, dimg_dev, err); });
 }
 int32_t vitx_nest_profile_begin(vitx_nest_handle m) {
-  CAPI_TRY
   if (!m) return capi_fail(VITX_ERR_INVALID, "null handle");
-  for (size_t i = 0; i < m->lv.size(); ++i) {
-    if (!m->lv[i].eng) continue;
-    const int rc = vitx_profile_begin(m->lv[i].eng);
-    if (rc == VITX_OK) continue;
-    for (size_t j = 0; j < i; ++j)   // leave no engine profiling behind a failure
-      if (m->lv[j].eng) (void)vitx_profile_end(m->lv[j].eng, nullptr, 0, nullptr);
-    return rc;
-  }
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_profile_begin(nest_engines(m));
 }
-// the levels' engines each keep their own classes: the same class of several levels is summed
 int32_t vitx_nest_profile_end(vitx_nest_handle m, vitx_kernel_stat* out, int32_t cap, int32_t* n_out) {
-  CAPI_TRY
   if (!m) return capi_fail(VITX_ERR_INVALID, "null handle");
-  std::vector<vitx_kernel_stat> all, one(256);
-  int first_err = VITX_OK;
-  std::map<std::string, size_t> at;
-  for (NestLevel& L : m->lv) {
-    if (!L.eng) continue;
-    int32_t k = 0;
-    const int rc = vitx_profile_end(L.eng, one.data(), (int32_t)one.size(), &k);
-    if (rc != VITX_OK) { if (first_err == VITX_OK) first_err = rc; continue; }   // (the other levels still stop profiling and release their events)
-    for (int32_t j = 0; j < std::min<int32_t>(k, (int32_t)one.size()); ++j) {
-      const auto it = at.find(one[(size_t)j].name);
-      if (it == at.end()) { at[one[(size_t)j].name] = all.size(); all.push_back(one[(size_t)j]); continue; }
-      vitx_kernel_stat& t = all[it->second];
-      t.launches += one[(size_t)j].launches; t.total_ms += one[(size_t)j].total_ms; t.flops += one[(size_t)j].flops; t.bytes += one[(size_t)j].bytes;
-    }
-  }
-  if (first_err != VITX_OK) return first_err;
-  for (size_t j = 0; j < all.size() && out && (int32_t)j < cap; ++j) out[j] = all[j];
-  if (n_out) *n_out = (int32_t)all.size();
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_profile_end(nest_engines(m), out, cap, n_out);
 }
 int32_t vitx_nest_read(vitx_nest_handle m, const char* which, float* out_host, int64_t cap, int64_t* n_elems) {
   CAPI_TRY
@@ -556,11 +470,7 @@ int32_t vitx_nest_read(vitx_nest_handle m, const char* which, float* out_host, i
   else if ((i = level_of("level.")) >= 0) { const NestLevel& L = m->lv[(size_t)i]; src = L.out; n = b * L.f * L.f * L.d; }
   else if ((i = level_of("aggregated.")) >= 0 && m->lv[(size_t)i].dn) { const NestLevel& L = m->lv[(size_t)i]; src = L.pooled; n = b * (L.f / 2) * (L.f / 2) * L.dn; }
   else return capi_fail(VITX_ERR_INVALID, "unknown tensor name");
-  if (n_elems) *n_elems = n;
-  if (n > cap) return capi_fail(VITX_ERR_INVALID, "output buffer too small");
-  CAPI_HIP(hipMemcpyAsync(out_host, src, (size_t)n * 4, hipMemcpyDeviceToHost, m->stream));
-  CAPI_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
+  return composite_read_tail(src, n, out_host, cap, n_elems, m->stream);
   CAPI_CATCH
 }
 

@@ -12,17 +12,12 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 
 #include "composite.h"
-#include "conv_same.h"
 
 namespace {
 
 constexpr int TW_STAGES = 4, TW_HEADS = 8, TW_DIM_HEAD = 64, TW_INNER = TW_HEADS * TW_DIM_HEAD, TW_MULT = 4;   // twins_svt.py:79,118,159
-
-// a tensor of the composite's arena and where it lives in an engine's: `rows` pieces of `width` floats, `epitch` apart in the engine
-struct TwinsMap { int64_t c, e, rows, width, epitch; };
 
 struct TwinsStage {
   int d = 0, p = 0, lp = 0, gk = 0, depth = 0, has_local = 0;   // s{i}_emb_dim, _patch_size, _local_patch_size, _global_k, _depth
@@ -30,7 +25,7 @@ struct TwinsStage {
   int Hin = 0, Win = 0, H = 0, W = 0;                           // the stage's input map and its own
   int64_t emb_w = -1, emb_b = -1, peg_w = -1, peg_b = -1;       // arena offsets
   vitx_engine *loc = nullptr, *glb = nullptr;
-  std::vector<TwinsMap> loc_maps, glb_maps;
+  std::vector<ArenaMap> loc_maps, glb_maps;
   float *x_in = nullptr, *patches = nullptr, *emb = nullptr, *pre_peg = nullptr, *peg_out = nullptr, *out = nullptr;
 };
 
@@ -188,11 +183,6 @@ void twins_destroy(vitx_twins* m) {
   delete m;
 }
 
-const ParamDesc* find_desc(const std::vector<ParamDesc>& t, const std::string& n) {
-  for (const auto& p : t) if (p.name == n) return &p;
-  return nullptr;
-}
-
 // parameter maps of one stage: composite tensor -> engine tensor, block l of the engines = layer l of the stage (0: transformer.0.0, l >= 1: transformer.1.(l - 1))
 int twins_maps(vitx_twins* m, size_t si, std::string& err) {
   TwinsStage& S = m->st[si];
@@ -204,24 +194,19 @@ int twins_maps(vitx_twins* m, size_t si, std::string& err) {
     const std::string eq = "transformer." + std::to_string(l) + ".";
     for (int g = S.has_local ? 0 : 1; g < 2; ++g) {
       vitx_engine* eng = g ? S.glb : S.loc;
-      std::vector<TwinsMap>& maps = g ? S.glb_maps : S.loc_maps;
+      std::vector<ArenaMap>& maps = g ? S.glb_maps : S.loc_maps;
       const std::string a = q + (g ? ".global_attn." : ".local_attn."), f = q + (g ? ".ff2." : ".ff1.");
-      auto plain = [&](const std::string& cn, const std::string& en) -> bool {
-        const ParamDesc *cp = find_desc(m->table, cn), *ep = find_desc(eng->table, en);
-        if (!cp || !ep || cp->count != ep->count) { err = "internal: parameter map " + cn + " -> " + en; return false; }
-        maps.push_back({cp->aoff, ep->aoff, 1, cp->count, cp->count});
-        return true;
+      auto add = [&](const std::string& cn, const std::string& en, int64_t col0 = 0, int64_t width = -1) {
+        return add_arena_map(maps, m->table, cn, eng->table, en, err, col0, width) == VITX_OK;
       };
-      for (const auto& pr : COMMON) if (!plain(a + pr[0], eq + pr[1])) return VITX_ERR_INVALID;
-      for (const auto& pr : FF) if (!plain(f + pr[0], eq + pr[1])) return VITX_ERR_INVALID;
+      for (const auto& pr : COMMON) if (!add(a + pr[0], eq + pr[1])) return VITX_ERR_INVALID;
+      for (const auto& pr : FF) if (!add(f + pr[0], eq + pr[1])) return VITX_ERR_INVALID;
       if (g) {
-        if (!plain(a + "to_q.kernel", eq + "attn.to_q.kernel") || !plain(a + "to_kv.kernel", eq + "attn.to_kv.kernel")) return VITX_ERR_INVALID;
+        if (!add(a + "to_q.kernel", eq + "attn.to_q.kernel") || !add(a + "to_kv.kernel", eq + "attn.to_kv.kernel")) return VITX_ERR_INVALID;
       } else {
         // to_qkv = [to_q | to_kv] column-wise (twins_svt.py:142-144 against nest.py:99): d rows of inner and 2 * inner floats into rows of 3 * inner
-        const ParamDesc *cq = find_desc(m->table, a + "to_q.kernel"), *ckv = find_desc(m->table, a + "to_kv.kernel"), *ep = find_desc(eng->table, eq + "attn.to_qkv.kernel");
-        if (!cq || !ckv || !ep || cq->count + ckv->count != ep->count) { err = "internal: parameter map " + a + "to_q / to_kv -> to_qkv"; return VITX_ERR_INVALID; }
-        maps.push_back({cq->aoff, ep->aoff, S.d, TW_INNER, 3 * TW_INNER});
-        maps.push_back({ckv->aoff, ep->aoff + TW_INNER, S.d, 2 * TW_INNER, 3 * TW_INNER});
+        if (!add(a + "to_q.kernel", eq + "attn.to_qkv.kernel", 0, TW_INNER) || !add(a + "to_kv.kernel", eq + "attn.to_qkv.kernel", TW_INNER, 2 * TW_INNER))
+          return VITX_ERR_INVALID;
       }
     }
   }
@@ -275,31 +260,15 @@ int twins_create(const vitx_twins_config& cin, vitx_twins** out, std::string& er
   return VITX_OK;
 }
 
-int copy_maps(vitx_twins* m, vitx_engine* eng, const std::vector<TwinsMap>& maps, bool to_engine, std::string& err) {
-  for (const TwinsMap& t : maps) {
-    float* cp = (to_engine ? m->params : m->grads) + t.c;
-    float* ep = (to_engine ? eng->params : eng->grads) + t.e;
-    if (t.rows == 1) HIPCHK(hipMemcpyAsync(to_engine ? ep : cp, to_engine ? cp : ep, (size_t)t.width * 4, hipMemcpyDeviceToDevice, m->stream));
-    else if (to_engine) HIPCHK(hipMemcpy2DAsync(ep, (size_t)t.epitch * 4, cp, (size_t)t.width * 4, (size_t)t.width * 4, (size_t)t.rows, hipMemcpyDeviceToDevice, m->stream));
-    else HIPCHK(hipMemcpy2DAsync(cp, (size_t)t.width * 4, ep, (size_t)t.epitch * 4, (size_t)t.width * 4, (size_t)t.rows, hipMemcpyDeviceToDevice, m->stream));
-  }
-  return VITX_OK;
-}
 int push_params(vitx_twins* m, std::string& err) {
   int rc;
   for (TwinsStage& S : m->st) {
-    if (S.loc) { if ((rc = copy_maps(m, S.loc, S.loc_maps, true, err)) != VITX_OK) return rc; S.loc->params_dirty = true; }
-    if ((rc = copy_maps(m, S.glb, S.glb_maps, true, err)) != VITX_OK) return rc;
+    if (S.loc) { if ((rc = copy_maps(m->params, S.loc->params, S.loc_maps, true, m->stream, err)) != VITX_OK) return rc; S.loc->params_dirty = true; }
+    if ((rc = copy_maps(m->params, S.glb->params, S.glb_maps, true, m->stream, err)) != VITX_OK) return rc;
     S.glb->params_dirty = true;
   }
   return VITX_OK;
 }
-
-// a composite launch booked on the first engine's profiler
-struct TwinsProf {
-  CompositeProf p;
-  TwinsProf(vitx_twins* m, const char* name) : p(m->prof_eng, name) {}
-};
 
 // one layer of a stage: the local pair on the window sequences (when the stage has one), then the global pair on the map; in == out is allowed
 int twins_layer_fwd(vitx_twins* m, TwinsStage& S, int l, const float* in, float* out, int b, std::string& err) {
@@ -308,10 +277,10 @@ int twins_layer_fwd(vitx_twins* m, TwinsStage& S, int l, const float* in, float*
   const float* cur = in;
   if (S.loc) {
     const int gy = S.H / S.lp, gx = S.W / S.lp;
-    { TwinsProf pr(m, "twins_windows"); launch_nest_to_blocks(cur, nullptr, m->tok_a, b, gy, S.lp, S.lp, S.d, s, gx); }   // twins_svt.py:141
+    { CompositeProf pr(m->prof_eng, "twins_windows"); launch_nest_to_blocks(cur, nullptr, m->tok_a, b, gy, S.lp, S.lp, S.d, s, gx); }   // twins_svt.py:141
     S.loc->stream = s;
     if ((rc = engine_transformer_forward(S.loc, m->tok_a, b * gy * gx, S.lp * S.lp, 0, 0, m->tok_b, err, l, l + 1)) != VITX_OK) return rc;
-    { TwinsProf pr(m, "twins_windows"); launch_nest_from_blocks(m->tok_b, m->tok_a, b, gy, S.lp, S.lp, S.d, s, gx); }       // :153
+    { CompositeProf pr(m->prof_eng, "twins_windows"); launch_nest_from_blocks(m->tok_b, m->tok_a, b, gy, S.lp, S.lp, S.d, s, gx); }       // :153
     cur = m->tok_a;
   }
   S.glb->stream = s;
@@ -327,10 +296,10 @@ int twins_layer_bwd(vitx_twins* m, TwinsStage& S, int l, float* g, int b, std::s
   if (S.loc) {
     const int gy = S.H / S.lp, gx = S.W / S.lp;
     // the partition's VJP is its inverse map and the other way round
-    { TwinsProf pr(m, "twins_windows"); launch_nest_to_blocks(g, nullptr, m->tok_a, b, gy, S.lp, S.lp, S.d, s, gx); }
+    { CompositeProf pr(m->prof_eng, "twins_windows"); launch_nest_to_blocks(g, nullptr, m->tok_a, b, gy, S.lp, S.lp, S.d, s, gx); }
     S.loc->stream = s;
     if ((rc = engine_transformer_backward(S.loc, m->tok_a, m->tok_b, err, l, l + 1)) != VITX_OK) return rc;
-    { TwinsProf pr(m, "twins_windows"); launch_nest_from_blocks(m->tok_b, g, b, gy, S.lp, S.lp, S.d, s, gx); }
+    { CompositeProf pr(m->prof_eng, "twins_windows"); launch_nest_from_blocks(m->tok_b, g, b, gy, S.lp, S.lp, S.d, s, gx); }
   }
   return VITX_OK;
 }
@@ -348,18 +317,18 @@ int twins_forward(vitx_twins* m, const float* img_dev, int b, std::string& err) 
     const float* x_in = i == 0 ? img_dev : S.x_in;
     const int rows = b * S.H * S.W;
     {   // PatchEmbedding (twins_svt.py:101-106)
-      TwinsProf pr(m, "twins_embed");
+      CompositeProf pr(m->prof_eng, "twins_embed");
       launch_twins_patch_gather(x_in, S.patches, b, S.Hin, S.Win, S.cin, S.p, S.pd, s);
       dense_fwd(S.patches, S.pd, P + S.emb_w, P + S.emb_b, S.emb, rows, S.d, S.pd, s, m->x3);
     }
     if ((rc = twins_layer_fwd(m, S, 0, S.emb, S.pre_peg, b, err)) != VITX_OK) return rc;   // Transformer(depth = 1)
-    { TwinsProf pr(m, "twins_peg_fwd"); launch_twins_peg_fwd(S.pre_peg, P + S.peg_w, P + S.peg_b, S.peg_out, b, S.H, S.W, S.d, m->kp, s); }
+    { CompositeProf pr(m->prof_eng, "twins_peg_fwd"); launch_twins_peg_fwd(S.pre_peg, P + S.peg_w, P + S.peg_b, S.peg_out, b, S.H, S.W, S.d, m->kp, s); }
     for (int l = 1; l < S.L; ++l)                                                          // Transformer(depth = s_depth)
       if ((rc = twins_layer_fwd(m, S, l, l == 1 ? S.peg_out : S.out, S.out, b, err)) != VITX_OK) return rc;
   }
   // GlobalAvgPool2D + Dense (:261-264)
   const TwinsStage& last = m->st.back();
-  TwinsProf pr(m, "twins_head");
+  CompositeProf pr(m->prof_eng, "twins_head");
   launch_mean_pool(last.out, b, last.H * last.W, last.d, m->pooled, s);
   dense_fwd(m->pooled, last.d, P + m->fc_w, P + m->fc_b, m->logits, b, m->nc, last.d, s);
   m->have_fwd = true;
@@ -378,7 +347,7 @@ int twins_backward(vitx_twins* m, const float* dlogits_dev, float* dimg_dev, std
   {
     const TwinsStage& last = m->st.back();
     const int d = last.d;
-    TwinsProf pr(m, "twins_head");
+    CompositeProf pr(m->prof_eng, "twins_head");
     dense_dw(m->pooled, d, dlogits_dev, G + m->fc_w, b, m->nc, d, s);
     launch_colsum(dlogits_dev, 0, m->nc, b, m->nc, m->ws, G + m->fc_b, s);
     dense_dx(dlogits_dev, P + m->fc_w, m->dpooled, b, m->nc, d, s);
@@ -391,17 +360,17 @@ int twins_backward(vitx_twins* m, const float* dlogits_dev, float* dimg_dev, std
     for (int l = S.L - 1; l >= 1; --l)
       if ((rc = twins_layer_bwd(m, S, l, g, b, err)) != VITX_OK) return rc;
     {   // PEG: g = d(peg_out) -> g2 = d(pre_peg)
-      TwinsProf pr(m, "twins_peg_bwd");
+      CompositeProf pr(m->prof_eng, "twins_peg_bwd");
       launch_colsum(g, 0, S.d, rows, S.d, m->ws, G + S.peg_b, s);
       launch_twins_peg_bwd_dkern(S.pre_peg, g, m->ws, G + S.peg_w, b, S.H, S.W, S.d, m->kp, s);
       launch_twins_peg_bwd_dx(g, P + S.peg_w, g2, b, S.H, S.W, S.d, m->kp, s);
       std::swap(g, g2);
     }
     if ((rc = twins_layer_bwd(m, S, 0, g, b, err)) != VITX_OK) return rc;
-    if (S.loc && (rc = copy_maps(m, S.loc, S.loc_maps, false, err)) != VITX_OK) return rc;
-    if ((rc = copy_maps(m, S.glb, S.glb_maps, false, err)) != VITX_OK) return rc;
+    if (S.loc && (rc = copy_maps(G, S.loc->grads, S.loc_maps, false, s, err)) != VITX_OK) return rc;
+    if ((rc = copy_maps(G, S.glb->grads, S.glb_maps, false, s, err)) != VITX_OK) return rc;
     // PatchEmbedding: g = d(emb)
-    TwinsProf pr(m, "twins_embed");
+    CompositeProf pr(m->prof_eng, "twins_embed");
     dense_dw(S.patches, S.pd, g, G + S.emb_w, rows, S.d, S.pd, s, m->x3);
     launch_colsum(g, 0, S.d, rows, S.d, m->ws, G + S.emb_b, s);
     if (i == 0 && !dimg_dev) break;
@@ -423,37 +392,17 @@ std::vector<vitx_engine*> twins_engines(vitx_twins* m) {
 extern "C" {
 
 int32_t vitx_twins_param_table_size(const vitx_twins_config* cfg, int64_t* n_tensors, int64_t* n_elems) {
-  CAPI_TRY
   if (!cfg) return capi_fail(VITX_ERR_INVALID, "null argument");
-  std::vector<ParamDesc> t;
-  int64_t n = 0;
-  std::string e = twins_param_table(*cfg, t, &n, nullptr);
-  if (!e.empty()) return capi_fail(VITX_ERR_INVALID, e);
-  if (n_tensors) *n_tensors = (int64_t)t.size();
-  if (n_elems) *n_elems = n;
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_table_size(*cfg, n_tensors, n_elems, twins_param_table);
 }
 int32_t vitx_twins_param_table_entry(const vitx_twins_config* cfg, int64_t index, char* name, int32_t name_cap, int64_t shape[4], int32_t* rank,
                                      int64_t* offset_elems) {
-  CAPI_TRY
   if (!cfg) return capi_fail(VITX_ERR_INVALID, "null argument");
-  std::vector<ParamDesc> t;
-  std::string e = twins_param_table(*cfg, t, nullptr, nullptr);
-  if (!e.empty()) return capi_fail(VITX_ERR_INVALID, e);
-  return write_table_entry(t, index, name, name_cap, shape, rank, offset_elems);
-  CAPI_CATCH
+  return composite_table_entry(*cfg, index, name, name_cap, shape, rank, offset_elems, twins_param_table);
 }
 int32_t vitx_twins_create(const vitx_twins_config* cfg, vitx_twins_handle* out) {
-  CAPI_TRY
   if (!cfg || !out) return capi_fail(VITX_ERR_INVALID, "null argument");
-  std::string err;
-  vitx_twins* m = nullptr;
-  int rc = twins_create(*cfg, &m, err);
-  if (rc != VITX_OK) return capi_fail(rc, err);
-  *out = m;
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_create(*cfg, out, twins_create);
 }
 int32_t vitx_twins_destroy(vitx_twins_handle m) {
   CAPI_TRY
@@ -474,17 +423,9 @@ int32_t vitx_twins_forward_dev(vitx_twins_handle m, const float* img_dev, int32_
   CAPI_CATCH
 }
 int32_t vitx_twins_forward(vitx_twins_handle m, const float* img_host, int32_t b, float* logits_host) {
-  CAPI_TRY
   if (!m || !img_host || !logits_host) return capi_fail(VITX_ERR_INVALID, "null argument");
-  if (b <= 0 || b > m->cfg.max_batch) return capi_fail(VITX_ERR_INVALID, "batch must be in [1, max_batch]");
-  CAPI_HIP(hipMemcpyAsync(m->img, img_host, (size_t)b * m->cfg.image_h * m->cfg.image_w * 3 * 4, hipMemcpyHostToDevice, m->stream));
-  std::string err;
-  int rc = twins_forward(m, m->img, b, err);
-  if (rc != VITX_OK) return capi_fail(rc, err);
-  CAPI_HIP(hipMemcpyAsync(logits_host, m->logits, (size_t)b * m->nc * 4, hipMemcpyDeviceToHost, m->stream));
-  CAPI_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_forward_host(m, img_host, (int64_t)m->cfg.image_h * m->cfg.image_w * 3, b, logits_host,
+                                [&](std::string& err) { return twins_forward(m, m->img, b, err); });
 }
 int32_t vitx_twins_backward_dev(vitx_twins_handle m, const float* dlogits_dev, float* dimg_dev_or_null) {
   CAPI_TRY
@@ -496,56 +437,17 @@ int32_t vitx_twins_backward_dev(vitx_twins_handle m, const float* dlogits_dev, f
   CAPI_CATCH
 }
 int32_t vitx_twins_backward(vitx_twins_handle m, const float* dlogits_host, float* dimg_host_or_null) {
-  CAPI_TRY
   if (!m || !dlogits_host) return capi_fail(VITX_ERR_INVALID, "null argument");
-  if (!m->have_fwd) return capi_fail(VITX_ERR_STATE, "backward requires a preceding forward");
-  CAPI_HIP(hipMemcpyAsync(m->dlogits, dlogits_host, (size_t)m->b * m->nc * 4, hipMemcpyHostToDevice, m->stream));
-  std::string err;
-  int rc = twins_backward(m, m->dlogits, dimg_host_or_null ? m->dimg : nullptr, err);
-  if (rc != VITX_OK) return capi_fail(rc, err);
-  if (dimg_host_or_null)
-    CAPI_HIP(hipMemcpyAsync(dimg_host_or_null, m->dimg, (size_t)m->b * m->cfg.image_h * m->cfg.image_w * 3 * 4, hipMemcpyDeviceToHost, m->stream));
-  CAPI_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_backward_host(m, dlogits_host, dimg_host_or_null, (int64_t)m->cfg.image_h * m->cfg.image_w * 3,
+                                 [&](float* dimg_dev, std::string& err) { return twins_backward(m, m->dlogits, dimg_dev, err); });
 }
-
 int32_t vitx_twins_profile_begin(vitx_twins_handle m) {
-  CAPI_TRY
   if (!m) return capi_fail(VITX_ERR_INVALID, "null handle");
-  const std::vector<vitx_engine*> engs = twins_engines(m);
-  for (size_t i = 0; i < engs.size(); ++i) {
-    const int rc = vitx_profile_begin(engs[i]);
-    if (rc == VITX_OK) continue;
-    for (size_t j = 0; j < i; ++j) (void)vitx_profile_end(engs[j], nullptr, 0, nullptr);   // leave no engine profiling behind a failure
-    return rc;
-  }
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_profile_begin(twins_engines(m));
 }
-// the engines each keep their own classes: the same class of several engines is summed
 int32_t vitx_twins_profile_end(vitx_twins_handle m, vitx_kernel_stat* out, int32_t cap, int32_t* n_out) {
-  CAPI_TRY
   if (!m) return capi_fail(VITX_ERR_INVALID, "null handle");
-  std::vector<vitx_kernel_stat> all, one(256);
-  int first_err = VITX_OK;
-  std::map<std::string, size_t> at;
-  for (vitx_engine* eng : twins_engines(m)) {
-    int32_t k = 0;
-    const int rc = vitx_profile_end(eng, one.data(), (int32_t)one.size(), &k);
-    if (rc != VITX_OK) { if (first_err == VITX_OK) first_err = rc; continue; }   // (the other engines still stop profiling and release their events)
-    for (int32_t j = 0; j < std::min<int32_t>(k, (int32_t)one.size()); ++j) {
-      const auto it = at.find(one[(size_t)j].name);
-      if (it == at.end()) { at[one[(size_t)j].name] = all.size(); all.push_back(one[(size_t)j]); continue; }
-      vitx_kernel_stat& t = all[it->second];
-      t.launches += one[(size_t)j].launches; t.total_ms += one[(size_t)j].total_ms; t.flops += one[(size_t)j].flops; t.bytes += one[(size_t)j].bytes;
-    }
-  }
-  if (first_err != VITX_OK) return first_err;
-  for (size_t j = 0; j < all.size() && out && (int32_t)j < cap; ++j) out[j] = all[j];
-  if (n_out) *n_out = (int32_t)all.size();
-  return VITX_OK;
-  CAPI_CATCH
+  return composite_profile_end(twins_engines(m), out, cap, n_out);
 }
 int32_t vitx_twins_read(vitx_twins_handle m, const char* which, float* out_host, int64_t cap, int64_t* n_elems) {
   CAPI_TRY
@@ -568,11 +470,7 @@ int32_t vitx_twins_read(vitx_twins_handle m, const char* which, float* out_host,
   else if ((i = stage_of("stage.")) >= 0) src = m->st[(size_t)i].out;
   else return capi_fail(VITX_ERR_INVALID, "unknown tensor name");
   if (w != "pooled") { const TwinsStage& S = m->st[(size_t)i]; n = b * S.H * S.W * S.d; }
-  if (n_elems) *n_elems = n;
-  if (n > cap) return capi_fail(VITX_ERR_INVALID, "output buffer too small");
-  CAPI_HIP(hipMemcpyAsync(out_host, src, (size_t)n * 4, hipMemcpyDeviceToHost, m->stream));
-  CAPI_HIP(hipStreamSynchronize(m->stream));
-  return VITX_OK;
+  return composite_read_tail(src, n, out_host, cap, n_elems, m->stream);
   CAPI_CATCH
 }
 

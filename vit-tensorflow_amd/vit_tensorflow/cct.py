@@ -8,13 +8,10 @@ Only the deterministic path exists: `CCT.__call__(img, training=None)` with `tra
 hard-wires is active).  `training=True` needs both and raises NotImplementedError."""
 from __future__ import annotations
 
-import ctypes as C
-import math
-
 import numpy as np
 
 from . import _native as N
-from ._composite import NativeComposite, as_host, like
+from ._composite import NativeComposite
 
 
 def pair(t):
@@ -88,9 +85,7 @@ class CCT(NativeComposite):
 
         Engine-only keyword extras: compute='fp32'|'bf16'|'bf16x3', max_batch=int, device=int, seed=int (the initialisers' generator),
         conv_chunk=int (images per im2col pass of the tokenizer; default: sized from a fixed workspace)."""
-        compute, max_batch, device, seed, conv_chunk = (kwargs.pop(k, v) for k, v in (("compute", "fp32"), ("max_batch", None), ("device", 0),
-                                                                                      ("seed", None), ("conv_chunk", 0)))
-        assert compute in ("fp32", "bf16", "bf16x3"), "compute must be 'fp32' (parity), 'bf16' (throughput) or 'bf16x3'"
+        compute, max_batch, device, seed, conv_chunk = self._pop_extras(kwargs, strict=False, conv_chunk=0)   # (the rest: _classifier_kwargs)
         if args:   # cct.py:330-339 passes them behind its own keywords: the first one lands on seq_pool
             raise TypeError("TransformerClassifier() got multiple values for argument 'seq_pool'")
         cls_kw = self._classifier_kwargs(**kwargs)
@@ -105,22 +100,14 @@ class CCT(NativeComposite):
                          positional_embedding=N.CCT_POS[pe], in_planes=64, conv_chunk=conv_chunk).items():
             setattr(cfg, k, int(v))
         cfg.ln_eps = 1e-3   # Keras LayerNormalization default
-        cfg.compute = {"fp32": N.COMPUTE_FP32, "bf16": N.COMPUTE_BF16, "bf16x3": N.COMPUTE_BF16X3}[compute]
-        cfg.max_batch = int(max_batch or 0)
-        cfg.device_id = int(device)
-        self._cfg = cfg
-        self.compute = compute
         self.img_size = (int(img_height), int(img_width))
         self.n_input_channels = int(n_input_channels)
         self.num_classes = int(cls_kw["num_classes"])
         self.positional_embedding = pe
         self.embedding_dim = int(embedding_dim)
-        self._handle = None
-        self._table, self._n = N.cct_param_table(cfg)
+        table = N.cct_param_table(cfg)
         self.sequence_length = N.cct_sequence_length(cfg)
-        self._blob = np.zeros(self._n, dtype=np.float32)
-        self._device_newer = False
-        self._init_weights(np.random.default_rng(seed))
+        self._start(cfg, table, compute, max_batch, device, seed)
 
     @staticmethod
     def _classifier_kwargs(num_layers=12, num_heads=12, mlp_ratio=4.0, num_classes=1000, positional_embedding='sine', **swallowed):
@@ -134,25 +121,14 @@ class CCT(NativeComposite):
 
     # ---- initialisers: Keras Conv2D / Dense glorot_uniform, zeros; LayerNormalization ones / zeros; truncated normal, stddev 0.2 (cct.py:252)
     def _init_weights(self, rng: np.random.Generator) -> None:
-        for name, shape, off in self._table:
-            n = int(np.prod(shape))
-            leaf = name.split(".")[-1]
-            if leaf == "positional_emb":
-                v = rng.standard_normal(n)
+        def truncated_normal(rng, n):
+            v = rng.standard_normal(n)
+            bad = np.abs(v) > 2.0
+            while bad.any():   # tf.random.truncated_normal: values beyond two standard deviations are redrawn
+                v[bad] = rng.standard_normal(int(bad.sum()))
                 bad = np.abs(v) > 2.0
-                while bad.any():   # tf.random.truncated_normal: values beyond two standard deviations are redrawn
-                    v[bad] = rng.standard_normal(int(bad.sum()))
-                    bad = np.abs(v) > 2.0
-                v = 0.2 * v
-            elif leaf == "kernel":
-                recv = int(np.prod(shape[:-2])) if len(shape) > 2 else 1
-                lim = math.sqrt(6.0 / (recv * shape[-2] + recv * shape[-1]))
-                v = rng.uniform(-lim, lim, n)
-            elif leaf == "gamma":
-                v = np.ones(n)
-            else:  # bias / beta
-                v = np.zeros(n)
-            self._blob[off:off + n] = v.astype(np.float32)
+            return 0.2 * v
+        self._fill_blob(rng, ones=("gamma",), draws={"positional_emb": truncated_normal})
 
     # ---- forward
     def __call__(self, img, training=None, **kwargs):
@@ -161,31 +137,20 @@ class CCT(NativeComposite):
             raise NotImplementedError("CCT(training=True) needs dropout on the attention probabilities (rate 0.1, cct.py:132) and per-sample "
                                       "stochastic depth (rates up to 0.1, cct.py:74-91,161,170); neither is built.  Only the deterministic path "
                                       "(training falsy) is supported.")
-        x, proto = as_host(img)
-        if x.ndim != 4 or x.shape[3] != self.n_input_channels:
-            raise ValueError(f"expected NHWC images [b, H, W, {self.n_input_channels}]")
+        x, proto = self._nhwc(img, self.n_input_channels)
         b, H, W, _c = x.shape
         if (H, W) != self.img_size:
             raise ValueError(f"CCT was built for img_size {self.img_size}; got images of {(H, W)} (the positional embedding and the sequence "
                              "length belong to the constructed size)")
-        h = self._ensure_handle(b)
-        self._img_shape = (b, H, W, self.n_input_channels)
-        out = np.empty((b, self.num_classes), dtype=np.float32)
-        N.check(N.lib().vitx_cct_forward(h, x.ctypes.data_as(C.c_void_p), b, out.ctypes.data_as(C.c_void_p)))
-        return like(out, proto)
+        return self._forward(self._ensure_handle(b), x, proto)
 
     call = __call__
     predict = lambda self, img, **kw: self(img, training=False, **kw)
 
     def read(self, which: str) -> np.ndarray:
         """Tensors of the last forward for bisecting: 'tokens' / 'encoded' [b, n, dim], 'pool_weights' [b, n], 'pooled' [b, dim]."""
-        if self._handle is None:
-            raise N.VitxError(N.ERR_STATE, "read requires a preceding forward")
-        b = self._img_shape[0]
-        cap = b * self.sequence_length * self.embedding_dim
-        buf, n = np.empty(cap, dtype=np.float32), C.c_int64()
-        N.check(N.lib().vitx_cct_read(self._handle, which.encode(), buf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
-        out = buf[:n.value]
+        b = self._read_shape()[0]
+        out = self._read_raw(which, b * self.sequence_length * self.embedding_dim)
         return out.reshape(b, -1, self.embedding_dim) if which in ("tokens", "encoded") else out.reshape(b, -1)
 
     apply_gradients = NativeComposite.optimizer_step

@@ -3,13 +3,10 @@
 heads run in HIP behind the C ABI (csrc/cross_vit.hip); parameters are in the order of DESIGN.md section 7."""
 from __future__ import annotations
 
-import ctypes as C
-import math
-
 import numpy as np
 
 from . import _native as N
-from ._composite import NativeComposite, as_host, like
+from ._composite import NativeComposite, as_host
 
 
 class CrossViT(NativeComposite):
@@ -33,34 +30,14 @@ class CrossViT(NativeComposite):
             setattr(cfg, k, int(v))
         cfg.dropout, cfg.emb_dropout = float(dropout), float(emb_dropout)
         cfg.ln_eps = 1e-3   # Keras LayerNormalization default
-        cfg.compute = {"fp32": N.COMPUTE_FP32, "bf16": N.COMPUTE_BF16, "bf16x3": N.COMPUTE_BF16X3}[compute]
-        cfg.max_batch = int(max_batch or 0)
-        cfg.device_id = int(device)
-        self._cfg = cfg
-        self.compute = compute
         self.image_size, self.num_classes = image_size, num_classes
         self.sm_patch_size, self.lg_patch_size = sm_patch_size, lg_patch_size
-        self._handle = None
-        self._table, self._n = N.crossvit_param_table(cfg)
-        self._blob = np.zeros(self._n, dtype=np.float32)
-        self._device_newer = False
-        self._init_weights(np.random.default_rng(seed))
+        self._start(cfg, N.crossvit_param_table(cfg), compute, max_batch, device, seed)
 
     # ---- initialisers: tf.random.normal (cross_vit.py:216-217), Keras Dense glorot_uniform / zeros, LayerNormalization ones / zeros
     def _init_weights(self, rng: np.random.Generator) -> None:
-        for name, shape, off in self._table:
-            n = int(np.prod(shape))
-            leaf = name.split(".")[-1]
-            if leaf in ("pos_embedding", "cls_token"):
-                v = rng.standard_normal(n)
-            elif leaf == "kernel":
-                lim = math.sqrt(6.0 / (shape[0] + shape[1]))
-                v = rng.uniform(-lim, lim, n)
-            elif leaf == "gamma":
-                v = np.ones(n)
-            else:  # bias / beta
-                v = np.zeros(n)
-            self._blob[off:off + n] = v.astype(np.float32)
+        normal = lambda rng, n: rng.standard_normal(n)
+        self._fill_blob(rng, ones=("gamma",), draws={"pos_embedding": normal, "cls_token": normal})
 
     # ---- forward
     def __call__(self, img, training=True, seed=None, **_):
@@ -71,27 +48,17 @@ class CrossViT(NativeComposite):
         b, H, W, _ = x.shape
         for p in (self.sm_patch_size, self.lg_patch_size):
             assert H % p == 0 and W % p == 0, 'Image dimensions must be divisible by the patch size.'
-        h = self._ensure_handle(b)
-        self._img_shape = (b, H, W, 3)
-        out = np.empty((b, self.num_classes), dtype=np.float32)
         seed = int(np.random.randint(0, 2 ** 31 - 1)) if seed is None else int(seed)
-        N.check(N.lib().vitx_crossvit_forward(h, x.ctypes.data_as(C.c_void_p), b, H, W, 1 if training else 0, seed,
-                                              out.ctypes.data_as(C.c_void_p)))
-        return like(out, proto)
+        return self._forward(self._ensure_handle(b), x, proto, H, W, 1 if training else 0, seed)
 
     call = __call__
     predict = lambda self, img, **kw: self(img, training=False, **kw)
 
     def read(self, which: str) -> np.ndarray:
         """Tensors of the last forward for bisecting: 'sm_tokens' / 'lg_tokens' [b, n, dim], 'sm_logits' / 'lg_logits' [b, num_classes]."""
-        if self._handle is None:
-            raise N.VitxError(N.ERR_STATE, "read requires a preceding forward")
-        b, H, W, _ = self._img_shape
-        cap = b * max(self.num_classes, max((H // p) * (W // p) + 1 for p in (self.sm_patch_size, self.lg_patch_size)) *
-                      max(self._cfg.sm_dim, self._cfg.lg_dim))
-        buf, n = np.empty(cap, dtype=np.float32), C.c_int64()
-        N.check(N.lib().vitx_crossvit_read(self._handle, which.encode(), buf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
-        out = buf[:n.value]
+        b, H, W, _ = self._read_shape()
+        out = self._read_raw(which, b * max(self.num_classes, max((H // p) * (W // p) + 1 for p in (self.sm_patch_size, self.lg_patch_size)) *
+                                            max(self._cfg.sm_dim, self._cfg.lg_dim)))
         if which.endswith("_logits"):
             return out.reshape(b, self.num_classes)
         dim = self._cfg.sm_dim if which.startswith("sm") else self._cfg.lg_dim

@@ -18,19 +18,16 @@ average, Keras 3 the biased one -- so a training forward leaves them as they are
 Only the deterministic path exists: `dropout > 0` with a truthy `training` raises NotImplementedError."""
 from __future__ import annotations
 
-import ctypes as C
-import math
-
 import numpy as np
 
 from . import _native as N
-from ._composite import NativeComposite, _Weight, as_host, like
+from ._composite import ImageSizedComposite, NativeComposite, _Weight
 
 _STAGE_KEYS = ("emb_dim", "emb_kernel", "emb_stride", "proj_kernel", "kv_proj_stride", "heads", "depth", "mlp_mult")
 _MOVING = ("moving_mean", "moving_variance")
 
 
-class CvT(NativeComposite):
+class CvT(ImageSizedComposite):
     _PREFIX, _NAME = "vitx_cvt", "CvT"
 
     def __init__(self, num_classes,
@@ -46,11 +43,7 @@ class CvT(NativeComposite):
         kernels of the bf16 mode: few-key for at most 64 keys, many-key for 65 .. 320; None: per class, where they measured faster than the
         materialised path -- DESIGN.md section 22; True: wherever they apply; False: nowhere.  More keys -- stage 1 of the usage has 784 --
         and the fp32 / bf16x3 modes run the materialised attention)."""
-        compute, max_batch, device, seed, image_size, fused_attn = (kwargs.pop(k, v) for k, v in (
-            ("compute", "fp32"), ("max_batch", None), ("device", 0), ("seed", None), ("image_size", None), ("fused_attn", None)))
-        if kwargs:
-            raise TypeError(f"CvT() got an unexpected keyword argument '{next(iter(kwargs))}'")
-        assert compute in ("fp32", "bf16", "bf16x3"), "compute must be 'fp32' (parity), 'bf16' (throughput) or 'bf16x3'"
+        compute, max_batch, device, seed, image_size, fused_attn = self._pop_extras(kwargs, image_size=None, fused_attn=None)
         a = dict(locals())
         stages = [tuple(int(a[f"s{i}_{k}"]) for k in _STAGE_KEYS) for i in (1, 2, 3)]
         if compute == "bf16" and any(s[0] % 64 for s in stages):
@@ -62,41 +55,17 @@ class CvT(NativeComposite):
             (cfg.emb_dim[i], cfg.emb_kernel[i], cfg.emb_stride[i], cfg.proj_kernel[i], cfg.kv_proj_stride[i], cfg.heads[i], cfg.depth[i],
              cfg.mlp_mult[i]) = s
         cfg.ln_eps = cfg.bn_eps = 1e-5   # cvt.py:31,85
-        cfg.compute = {"fp32": N.COMPUTE_FP32, "bf16": N.COMPUTE_BF16, "bf16x3": N.COMPUTE_BF16X3}[compute]
-        cfg.max_batch = int(max_batch or 0)
-        cfg.device_id = int(device)
         cfg.fused_attn = 0 if fused_attn is None else (1 if fused_attn else -1)
-        self._cfg = cfg
-        self.compute = compute
         self.num_classes, self.stages, self.dropout = int(num_classes), stages, float(dropout)
-        self._handle = None
         self._last_training = True
-        try:
-            self._table, self._n = N.cvt_param_table(cfg)   # (no image yet: no parameter depends on one)
-        except N.VitxError as e:
-            raise ValueError(e.message) from None
-        self._blob = np.zeros(self._n, dtype=np.float32)
-        self._device_newer = False
-        self._init_weights(np.random.default_rng(seed))
-        if image_size is not None:
-            H, W = (image_size, image_size) if isinstance(image_size, int) else image_size
-            self._ensure_handle(max(1, int(max_batch or 1)), int(H), int(W))
+        # (no image yet: no parameter depends on one)
+        self._start(cfg, self._refused_as_value_error(N.cvt_param_table, cfg), compute, max_batch, device, seed)
+        self._eager_handle(image_size, max_batch)
 
     # ---- initialisers: Keras Conv2D / Dense glorot_uniform with the kernel's own fans, zeros; LayerNorm and BatchNormalization ones / zeros,
     # moving statistics 0 / 1
     def _init_weights(self, rng: np.random.Generator) -> None:
-        for name, shape, off in self._table:
-            n = int(np.prod(shape))
-            leaf = name.split(".")[-1]
-            if leaf == "kernel":
-                recv = int(np.prod(shape[:-2])) if len(shape) > 2 else 1
-                lim = math.sqrt(6.0 / (recv * shape[-2] + recv * shape[-1]))
-                v = rng.uniform(-lim, lim, n)
-            elif leaf in ("g", "gamma", "moving_variance"):
-                v = np.ones(n)
-            else:  # bias / b / beta / moving_mean
-                v = np.zeros(n)
-            self._blob[off:off + n] = v.astype(np.float32)
+        self._fill_blob(rng, ones=("g", "gamma", "moving_variance"))
 
     # ---- the moving statistics are state, not trainable variables
     @property
@@ -114,22 +83,9 @@ class CvT(NativeComposite):
             out.append(((H, W), (-(-H // ks), -(-W // ks))))
         return out
 
-    def _ensure_handle(self, batch: int, H: int | None = None, W: int | None = None):
-        """The handle for (H, W) images of up to `batch`; built again, weights kept, when the image size changes or a larger batch arrives."""
-        if H is None:
-            H, W = int(self._cfg.image_h), int(self._cfg.image_w)
-            if H == 0:
-                raise N.VitxError(N.ERR_STATE, "CvT has no native handle before its first call (pass image_size= to create it eagerly)")
-        if self._handle is not None and (H, W) == (self._cfg.image_h, self._cfg.image_w):
-            return super()._ensure_handle(batch)
+    def _check_image(self, H: int, W: int) -> None:
         if H <= 0 or W <= 0:
             raise ValueError("image height and width must be positive")
-        if self._handle is not None:
-            self._pull_params()
-            N.check(self._native("destroy")(self._handle))
-            self._handle = None
-        self._cfg.image_h, self._cfg.image_w = int(H), int(W)
-        return super()._ensure_handle(batch)
 
     # ---- forward
     def __call__(self, img, training=True, **kwargs):
@@ -138,16 +94,10 @@ class CvT(NativeComposite):
             raise NotImplementedError(f"CvT(dropout={self.dropout}) with training=True needs the Dropout masks of cvt.py:70,72,108; they are not "
                                       "built.  Call with training=False, or construct with dropout=0.0 (then training=True is the deterministic "
                                       "path).")
-        x, proto = as_host(img)
-        if x.ndim != 4 or x.shape[3] != 3:
-            raise ValueError("expected NHWC images [b, H, W, 3]")
-        b, H, W, _c = x.shape
-        h = self._ensure_handle(b, H, W)
-        self._img_shape = (b, H, W, 3)
+        x, proto = self._nhwc(img)
+        h = self._ensure_handle(*x.shape[:3])
         self._last_training = bool(training)
-        out = np.empty((b, self.num_classes), dtype=np.float32)
-        N.check(N.lib().vitx_cvt_forward(h, x.ctypes.data_as(C.c_void_p), b, 1 if training else 0, out.ctypes.data_as(C.c_void_p)))
-        return like(out, proto)
+        return self._forward(h, x, proto, 1 if training else 0)
 
     call = __call__
     predict = lambda self, img, **kw: self(img, training=False, **kw)
@@ -163,29 +113,13 @@ class CvT(NativeComposite):
         """Tensors of the last forward for bisecting: 'embedded.<s>' (stage s's embedding behind its LayerNorm) and 'stage.<s>' (its output),
         [b, H_s, W_s, emb_dim_s]; 'q_in.<s>.<l>' [b, H_s, W_s, emb_dim_s] and 'kv_in.<s>.<l>' [b, kv H_s, kv W_s, emb_dim_s] (the inputs of
         layer l's pointwise projections, behind BatchNormalization); 'pooled' [b, emb_dim_3]."""
-        if self._handle is None:
-            raise N.VitxError(N.ERR_STATE, "read requires a preceding forward")
-        b, H, W, _ = self._img_shape
+        b, H, W, _ = self._read_shape()
         maps = self.maps_of(H, W)
-        cap = b * max(h * w * s[0] for ((h, w), _kv), s in zip(maps, self.stages))
-        buf, n = np.empty(cap, dtype=np.float32), C.c_int64()
-        N.check(N.lib().vitx_cvt_read(self._handle, which.encode(), buf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
-        out = buf[:n.value]
+        out = self._read_raw(which, b * max(h * w * s[0] for ((h, w), _kv), s in zip(maps, self.stages)))
         if which == "pooled":
             return out.reshape(b, -1)
         full, kv = maps[int(which.split(".")[1])]
         h, w = kv if which.startswith("kv_in.") else full
         return out.reshape(b, h, w, -1)
-
-    def profile(self, fn):
-        """Runs fn() between vitx_cvt_profile_begin / _end: {class: (launches, total_ms)}."""
-        h = self._ensure_handle(1)
-        N.check(N.lib().vitx_cvt_profile_begin(h))
-        try:
-            fn()
-        finally:
-            stats, n = (N.KernelStat * 256)(), C.c_int32()
-            N.check(N.lib().vitx_cvt_profile_end(h, stats, 256, C.byref(n)))
-        return {stats[i].name.decode(): (int(stats[i].launches), float(stats[i].total_ms)) for i in range(min(n.value, 256))}
 
     apply_gradients = NativeComposite.optimizer_step

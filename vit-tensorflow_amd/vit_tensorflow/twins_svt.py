@@ -11,16 +11,13 @@ Only the deterministic path exists: `dropout == 0`, where `training=True` (the r
 thing.  `dropout > 0` with a truthy `training` raises NotImplementedError."""
 from __future__ import annotations
 
-import ctypes as C
-import math
-
 import numpy as np
 
 from . import _native as N
-from ._composite import NativeComposite, as_host, like
+from ._composite import ImageSizedComposite, NativeComposite
 
 
-class TwinsSVT(NativeComposite):
+class TwinsSVT(ImageSizedComposite):
     _PREFIX, _NAME = "vitx_twins", "TwinsSVT"
 
     def __init__(self, num_classes,
@@ -38,11 +35,7 @@ class TwinsSVT(NativeComposite):
         image_size=int|(H, W) (create the native handle now instead of at the first call), fused_global_attn=None|True|False (the few-key
         attention kernels of the global pairs: bf16 mode, at most 64 keys; None: where they measured faster than the materialised path --
         DESIGN.md section 21; True: wherever they apply; False: nowhere)."""
-        compute, max_batch, device, seed, image_size, fused_global_attn = (kwargs.pop(k, v) for k, v in (
-            ("compute", "fp32"), ("max_batch", None), ("device", 0), ("seed", None), ("image_size", None), ("fused_global_attn", None)))
-        if kwargs:
-            raise TypeError(f"TwinsSVT() got an unexpected keyword argument '{next(iter(kwargs))}'")
-        assert compute in ("fp32", "bf16", "bf16x3"), "compute must be 'fp32' (parity), 'bf16' (throughput) or 'bf16x3'"
+        compute, max_batch, device, seed, image_size, fused_global_attn = self._pop_extras(kwargs, image_size=None, fused_global_attn=None)
         a = dict(locals())
         stages = [tuple(int(a[f"s{i}_{k}"]) for k in ("emb_dim", "patch_size", "local_patch_size", "global_k", "depth")) for i in (1, 2, 3, 4)]
         if int(peg_kernel_size) <= 0 or int(peg_kernel_size) % 2 == 0:
@@ -56,70 +49,29 @@ class TwinsSVT(NativeComposite):
             cfg.emb_dim[i], cfg.patch_size[i], cfg.local_patch_size[i], cfg.global_k[i], cfg.depth[i] = s
         cfg.peg_kernel_size = int(peg_kernel_size)
         cfg.ln_eps = 1e-5   # twins_svt.py:46
-        cfg.compute = {"fp32": N.COMPUTE_FP32, "bf16": N.COMPUTE_BF16, "bf16x3": N.COMPUTE_BF16X3}[compute]
-        cfg.max_batch = int(max_batch or 0)
-        cfg.device_id = int(device)
         cfg.fused_global_attn = 0 if fused_global_attn is None else (1 if fused_global_attn else -1)
-        self._cfg = cfg
-        self.compute = compute
         self.num_classes, self.stages, self.peg_kernel_size, self.dropout = int(num_classes), stages, int(peg_kernel_size), float(dropout)
-        self._handle = None
-        try:
-            self._table, self._n = N.twins_param_table(cfg)   # (no image yet: no parameter depends on one)
-        except N.VitxError as e:
-            raise ValueError(e.message) from None
-        self._blob = np.zeros(self._n, dtype=np.float32)
-        self._device_newer = False
-        self._init_weights(np.random.default_rng(seed))
-        if image_size is not None:
-            H, W = (image_size, image_size) if isinstance(image_size, int) else image_size
-            self._ensure_handle(max(1, int(max_batch or 1)), int(H), int(W))
+        # (no image yet: no parameter depends on one)
+        self._start(cfg, self._refused_as_value_error(N.twins_param_table, cfg), compute, max_batch, device, seed)
+        self._eager_handle(image_size, max_batch)
 
     # ---- initialisers: Keras Conv2D / Dense glorot_uniform, zeros; LayerNorm ones / zeros (twins_svt.py:50-51)
     def _init_weights(self, rng: np.random.Generator) -> None:
-        for name, shape, off in self._table:
-            n = int(np.prod(shape))
-            leaf = name.split(".")[-1]
-            if leaf == "kernel":
-                recv = int(np.prod(shape[:-2])) if len(shape) > 2 else 1
-                lim = math.sqrt(6.0 / (recv * shape[-2] + recv * shape[-1]))
-                v = rng.uniform(-lim, lim, n)
-            elif leaf == "g":
-                v = np.ones(n)
-            else:  # bias / b
-                v = np.zeros(n)
-            self._blob[off:off + n] = v.astype(np.float32)
+        self._fill_blob(rng, ones=("g",))
 
     # ---- geometry
     def maps_of(self, H: int, W: int):
         """[(H_s, W_s)] of the four stages for an H x W image; ValueError where a stage's patch_size, local_patch_size or global_k does not divide."""
         cfg = N.TwinsConfig.from_buffer_copy(self._cfg)
         cfg.image_h, cfg.image_w = int(H), int(W)
-        try:
-            N.twins_param_table(cfg)
-        except N.VitxError as e:
-            raise ValueError(e.message) from None
+        self._refused_as_value_error(N.twins_param_table, cfg)
         out = []
         for d, p, lp, gk, depth in self.stages:
             H, W = H // p, W // p
             out.append((H, W))
         return out
 
-    def _ensure_handle(self, batch: int, H: int | None = None, W: int | None = None):
-        """The handle for (H, W) images of up to `batch`; built again, weights kept, when the image size changes or a larger batch arrives."""
-        if H is None:
-            H, W = int(self._cfg.image_h), int(self._cfg.image_w)
-            if H == 0:
-                raise N.VitxError(N.ERR_STATE, "TwinsSVT has no native handle before its first call (pass image_size= to create it eagerly)")
-        if self._handle is not None and (H, W) == (self._cfg.image_h, self._cfg.image_w):
-            return super()._ensure_handle(batch)
-        self.maps_of(H, W)
-        if self._handle is not None:
-            self._pull_params()
-            N.check(self._native("destroy")(self._handle))
-            self._handle = None
-        self._cfg.image_h, self._cfg.image_w = int(H), int(W)
-        return super()._ensure_handle(batch)
+    _check_image = maps_of
 
     # ---- forward
     def __call__(self, img, training=True, **kwargs):
@@ -128,15 +80,8 @@ class TwinsSVT(NativeComposite):
             raise NotImplementedError(f"TwinsSVT(dropout={self.dropout}) with training=True needs the Dropout masks of twins_svt.py:85,87,132,172; "
                                       "they are not built.  Call with training=False, or construct with dropout=0.0 (then training=True is the "
                                       "deterministic path).")
-        x, proto = as_host(img)
-        if x.ndim != 4 or x.shape[3] != 3:
-            raise ValueError("expected NHWC images [b, H, W, 3]")
-        b, H, W, _c = x.shape
-        h = self._ensure_handle(b, H, W)
-        self._img_shape = (b, H, W, 3)
-        out = np.empty((b, self.num_classes), dtype=np.float32)
-        N.check(N.lib().vitx_twins_forward(h, x.ctypes.data_as(C.c_void_p), b, out.ctypes.data_as(C.c_void_p)))
-        return like(out, proto)
+        x, proto = self._nhwc(img)
+        return self._forward(self._ensure_handle(*x.shape[:3]), x, proto)
 
     call = __call__
     predict = lambda self, img, **kw: self(img, training=False, **kw)
@@ -144,28 +89,12 @@ class TwinsSVT(NativeComposite):
     def read(self, which: str) -> np.ndarray:
         """Tensors of the last forward for bisecting: 'embedded.<s>' (stage s's patch embedding), 'pre_peg.<s>' / 'peg.<s>' (in front of / behind
         its PEG), 'stage.<s>' (its output), each [b, H_s, W_s, emb_dim_s]; 'pooled' [b, emb_dim_4]."""
-        if self._handle is None:
-            raise N.VitxError(N.ERR_STATE, "read requires a preceding forward")
-        b, H, W, _ = self._img_shape
+        b, H, W, _ = self._read_shape()
         maps = self.maps_of(H, W)
-        cap = b * max(h * w * s[0] for (h, w), s in zip(maps, self.stages))
-        buf, n = np.empty(cap, dtype=np.float32), C.c_int64()
-        N.check(N.lib().vitx_twins_read(self._handle, which.encode(), buf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
-        out = buf[:n.value]
+        out = self._read_raw(which, b * max(h * w * s[0] for (h, w), s in zip(maps, self.stages)))
         if which == "pooled":
             return out.reshape(b, -1)
         h, w = maps[int(which.split(".")[1])]
         return out.reshape(b, h, w, -1)
-
-    def profile(self, fn):
-        """Runs fn() between vitx_twins_profile_begin / _end: {class: (launches, total_ms)}."""
-        h = self._ensure_handle(1)
-        N.check(N.lib().vitx_twins_profile_begin(h))
-        try:
-            fn()
-        finally:
-            stats, n = (N.KernelStat * 256)(), C.c_int32()
-            N.check(N.lib().vitx_twins_profile_end(h, stats, 256, C.byref(n)))
-        return {stats[i].name.decode(): (int(stats[i].launches), float(stats[i].total_ms)) for i in range(min(n.value, 256))}
 
     apply_gradients = NativeComposite.optimizer_step
