@@ -667,6 +667,76 @@ int32_t vitx_cvt_profile_end(vitx_cvt_handle m, vitx_kernel_stat* out, int32_t c
  * projections, behind BatchNormalization, widened to fp32); "pooled" [b, emb_dim_3] */
 int32_t vitx_cvt_read(vitx_cvt_handle m, const char* which, float* out_host, int64_t cap_elems, int64_t* n_elems);
 
+/* ---- CrossFormer (crossformer.py:205-257): four stages of CrossEmbedLayer (:30-48: one Conv2D 'SAME' with bias per kernel size, kernel sizes
+ * sorted, widths int(dim / 2^i) and the rest for the last, concatenated over channels; im2col + GEMM per scale) and a Transformer (:182-203) of
+ * `depth` layers x + short_attn(x), x + MLP(x), x + long_attn(x), x + MLP(x); then the mean over the map and Dense (:245-248).  Attention
+ * (:104-180) is a channel LayerNorm (eps 1e-5, :74-87), a window partition -- 'short': contiguous wsz x wsz windows (:144), 'long': the dilated
+ * partition 'b (l1 h) (l2 w) d -> (b h w) l1 l2 d' (:146) --, heads of 32 (:105: CrossFormer never passes dim_head; heads = dim // 32),
+ * softmax(scale q k^T + bias) v with the bias of the DynamicPositionBias network (:51-71) gathered through rel_pos_indices (:126-131,159-165),
+ * and to_out.  The bias network receives no gradient in the reference (:163 leaves the tape through .numpy()): its gradients are zeros.
+ * A stage's short pairs run on one vitx_config.nest_block engine over (b * windows) sequences of local^2 tokens, its long pairs on another over
+ * sequences of global^2 tokens; the bias reaches the small-head attention kernels' BIAS form through the engines.  A handle of its own;
+ * parameter order in DESIGN.md section 23.  Only the deterministic path (ff_dropout 0) exists; attn_dropout is unused by the reference. */
+#define VITX_CF_MAX_SCALES 8
+typedef struct vitx_crossformer_config {
+  /* the image the handle is built for; both 0 is allowed for the host-only table calls (no parameter depends on the image size) */
+  int32_t image_h, image_w;
+  int32_t num_classes;              /* crossformer.py:213 */
+  int32_t dim[4], depth[4], global_window_size[4], local_window_size[4];   /* :207-210 */
+  int32_t n_kernels[4];             /* :211: kernel sizes per stage, 1 .. VITX_CF_MAX_SCALES (any order: the library sorts them as :34 does) */
+  int32_t kernel_sizes[4][VITX_CF_MAX_SCALES];
+  int32_t strides[4];               /* :212 */
+  float ln_eps;                     /* <= 0: crossformer.py:75's 1e-5 */
+  int32_t compute;                  /* VITX_COMPUTE_*: the transformer blocks' mode; embeddings, bias network and head keep fp32 */
+  int32_t max_batch;
+  int32_t device_id;
+  /* the window attention kernels (attn_window.hip: bf16 mode, at most 64 tokens; one wave per (window, head), the bias staged in LDS, d(q, k, v)
+   * written by the same wave).  0: where they measured faster than the BIAS form of the small-head kernels at the usage shape (DESIGN.md
+   * section 23).  1: wherever they apply.  -1: nowhere.  More tokens, and the fp32 / bf16x3 modes, take the small-head kernels. */
+  int32_t window_attn;
+  int32_t reserved[7];
+} vitx_crossformer_config;
+typedef struct vitx_crossformer* vitx_crossformer_handle;
+/* host only, no GPU needed */
+int32_t vitx_crossformer_param_table_size(const vitx_crossformer_config* cfg, int64_t* n_tensors, int64_t* n_elems);
+int32_t vitx_crossformer_param_table_entry(const vitx_crossformer_config* cfg, int64_t index, char* name, int32_t name_cap, int64_t shape[4],
+                                           int32_t* rank, int64_t* offset_elems);
+int32_t vitx_crossformer_create(const vitx_crossformer_config* cfg, vitx_crossformer_handle* out);
+int32_t vitx_crossformer_destroy(vitx_crossformer_handle m);
+/* set_params / params_changed also evaluate every attention's bias network again (crossformer.py:159-163 does it per call; the bias is a
+ * function of the parameters alone) */
+int32_t vitx_crossformer_set_params(vitx_crossformer_handle m, const float* host_blob, int64_t n_elems);
+int32_t vitx_crossformer_get_params(vitx_crossformer_handle m, float* host_blob, int64_t n_elems);
+int32_t vitx_crossformer_get_grads(vitx_crossformer_handle m, float* host_blob, int64_t n_elems);
+int32_t vitx_crossformer_params_dev(vitx_crossformer_handle m, float** dev_ptr, int64_t* n_elems);
+int32_t vitx_crossformer_grads_dev(vitx_crossformer_handle m, float** dev_ptr, int64_t* n_elems);
+int32_t vitx_crossformer_params_changed(vitx_crossformer_handle m);
+/* CrossFormer.call (crossformer.py:250-257).  img [b, image_h, image_w, 3] NHWC; logits [b, num_classes] */
+int32_t vitx_crossformer_forward(vitx_crossformer_handle m, const float* img_host, int32_t b, float* logits_host);
+int32_t vitx_crossformer_forward_dev(vitx_crossformer_handle m, const float* img_dev, int32_t b, float* logits_dev_or_null);
+/* VJP of the last forward for d(logits): overwrites the gradient arena (the dpb.* entries with zeros, :163); d(img) only when asked for */
+int32_t vitx_crossformer_backward(vitx_crossformer_handle m, const float* dlogits_host, float* dimg_host_or_null);
+int32_t vitx_crossformer_backward_dev(vitx_crossformer_handle m, const float* dlogits_dev, float* dimg_dev_or_null);
+/* per-kernel-class timing of the steps between the two calls, as vitx_profile_begin / _end: every engine's block classes (attn_small_fwd / _bwd
+ * among them) plus the composite's own (cf_im2col, cf_conv_gemm, cf_col2im, cf_windows, cf_head) */
+int32_t vitx_crossformer_profile_begin(vitx_crossformer_handle m);
+int32_t vitx_crossformer_profile_end(vitx_crossformer_handle m, vitx_kernel_stat* out, int32_t cap, int32_t* n_out);
+/* "embedded.<s>" (the stage's cross-scale embedding, :45-48) and "stage.<s>" (its output), each [b, H_s, W_s, dim_s]; "pooled" [b, dim_4];
+ * "bias.<s>.<l>.short" / "bias.<s>.<l>.long": the [n, n] position bias of layer l's short / long attention (:163) */
+int32_t vitx_crossformer_read(vitx_crossformer_handle m, const char* which, float* out_host, int64_t cap_elems, int64_t* n_elems);
+/* The biased attention kernels alone, on host tensors, for tests and bisecting (crossformer.py:156-171 and its VJP on bf16 storage, heads of
+ * 32): qkv [b, n, 3, h, 32], d_o [b, n, h * 32], bias [n, n]; window_kernel != 0: attn_window.hip (1 <= n <= 64), 0: the BIAS form of the
+ * small-head kernels (n <= 288).  Every device activation buffer gets tail_rows extra rows behind its b * n live ones, filled with tail_value
+ * (NaN allowed) before the run; o_host [(b * n + tail_rows), h * 32] and dqkv_host [(b * n + tail_rows), 3 * h * 32] return the whole buffers
+ * (widened from bf16), so that a caller sees both that nothing past the live rows was read and that nothing past them was written;
+ * lse_host [b, h, n]. */
+int32_t vitx_crossformer_window_attn(vitx_crossformer_handle m, const float* qkv_host, const float* d_o_host, const float* bias_host, int32_t b, int32_t n,
+                                     int32_t h, int32_t tail_rows, float tail_value, int32_t window_kernel, float* o_host, float* lse_host, float* dqkv_host);
+/* the dilated partition kernel on a host tensor, for tests and bisecting: inverse == 0 is 'b (l1 h) (l2 w) c -> (b h w) (l1 l2) c' with
+ * l1 = l2 = g (crossformer.py:146) of in [b, H, W, c]; inverse != 0 is the way back (:178) of in [(b h w), (l1 l2), c] */
+int32_t vitx_crossformer_partition(vitx_crossformer_handle m, const float* in_host, float* out_host, int32_t b, int32_t H, int32_t W, int32_t g,
+                                   int32_t c, int32_t inverse);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,7 +70,7 @@ __device__ __forceinline__ void lsa_row_times_staged(const float* wrow, int npad
   }
 }
 
-template <typename T, int DH, int R, bool PLAIN>
+template <typename T, int DH, int R, bool PLAIN, bool BIAS = false>
 __global__ __launch_bounds__(256) void attn_lsa_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ o, float* __restrict__ lse,
                                                            const float* __restrict__ temperature, float scale, int n, int h) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -119,7 +119,11 @@ __global__ __launch_bounds__(256) void attn_lsa_fwd_kernel(const T* __restrict__
         }
       }
 #pragma unroll
-      for (int r = 0; r < R; ++r) s[r][jc] = j >= n ? -INFINITY : (!PLAIN && j == r0 + r ? -FLT_MAX : acc[r] * et);
+      for (int r = 0; r < R; ++r) {
+        float sv = acc[r] * et;
+        if (BIAS && j < n) sv += temperature[(int64_t)min(r0 + r, n - 1) * n + j];   // (BIAS: `temperature` is the [n, n] bias)
+        s[r][jc] = j >= n ? -INFINITY : (!PLAIN && j == r0 + r ? -FLT_MAX : sv);
+      }
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -161,7 +165,7 @@ __global__ __launch_bounds__(256) void attn_lsa_fwd_kernel(const T* __restrict__
 // and C[row 4 (l >> 4) + r][col l & 15].  S tile by tile stays in registers (18 tiles x 4 fp32 at n = 288); row maxima / sums are reduced over
 // the 16 lanes of a row group; P goes through a per-wave LDS tile as bf16 (un-normalised, the fp32 row sum divides the output) to become the
 // A operand of P v.
-template <int DH, bool PLAIN>
+template <int DH, bool PLAIN, bool BIAS = false>
 __global__ __launch_bounds__(256) void attn_lsa_fwd_mfma_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o, float* __restrict__ lse,
                                                                 const float* __restrict__ temperature, float scale, int n, int h) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -218,7 +222,8 @@ __global__ __launch_bounds__(256) void attn_lsa_fwd_mfma_kernel(const bf16_t* __
 #pragma unroll
     for (int jt = 0; jt < NT; ++jt) {
       const int j = jt * 16 + lr;
-      const float v = (j < n && (PLAIN || j != row)) ? s[jt][r] * et : -INFINITY;
+      float v = (j < n && (PLAIN || j != row)) ? s[jt][r] * et : -INFINITY;
+      if (BIAS && j < n) v += temperature[(int64_t)min(row, n - 1) * n + j];   // (BIAS: `temperature` is the [n, n] bias)
       s[jt][r] = v;
       m = fmaxf(m, v);
     }
@@ -255,9 +260,9 @@ template <int DH> size_t lsa_fwd_mfma_lds(int n) {
   const int DHP = DH < 32 ? 32 : DH, n16 = (n + 15) & ~15, PP = ((n + 31) & ~31) + 8;
   return ((size_t)n16 * (DHP + 8) + (size_t)DH * PP + (size_t)LSA_WAVES * 16 * PP) * 2;
 }
-template <int DH, bool PLAIN>
+template <int DH, bool PLAIN, bool BIAS = false>
 void lsa_fwd_mfma_launch(const bf16_t* qkv, bf16_t* o, float* lse, int b, int n, int h, const float* t, float scale, hipStream_t s) {
-  auto kern = attn_lsa_fwd_mfma_kernel<DH, PLAIN>;
+  auto kern = attn_lsa_fwd_mfma_kernel<DH, PLAIN, BIAS>;
   vitx_set_max_smem((const void*)kern, LSA_LDS_MAX);
   const size_t lds = lsa_fwd_mfma_lds<DH>(n);
   hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, lse, t, scale, n, h);
@@ -266,7 +271,7 @@ void lsa_fwd_mfma_launch(const bf16_t* qkv, bf16_t* o, float* lse, int b, int n,
 // KEYS = false: the tile's rows are queries, K and V are staged: d(q), the row sums D = dO . o (kept in dsum for the other pass) and this workgroup's
 //               partial of the temperature gradient.
 // KEYS = true:  the tile's rows are keys, Q and dO are staged: d(k) and d(v).
-template <typename T, int DH, int R, bool KEYS, bool PLAIN>
+template <typename T, int DH, int R, bool KEYS, bool PLAIN, bool BIAS = false>
 __global__ __launch_bounds__(256) void attn_lsa_bwd_kernel(const T* __restrict__ qkv, const T* __restrict__ o, const T* __restrict__ d_o,
                                                            const float* __restrict__ lse, float* __restrict__ dsum, T* __restrict__ dqkv,
                                                            const float* __restrict__ temperature, float scale, float* __restrict__ dt_part, int n,
@@ -348,7 +353,8 @@ __global__ __launch_bounds__(256) void attn_lsa_bwd_kernel(const T* __restrict__
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           const bool live = j < n && (PLAIN || j != r0 + r) && r0 + r < n;
-          const float sc = sa[r] * et;
+          float sc = sa[r] * et;
+          if (BIAS && live) sc += KEYS ? temperature[(int64_t)j * n + r0 + r] : temperature[(int64_t)(r0 + r) * n + j];   // bias[query][key]
           const float p = live ? expf(sc - (KEYS ? lj : lrow[r])) : 0.f;
           const float ds = p * (sb[r] - (KEYS ? Dj : Drow[r]));
           if (!KEYS && !PLAIN && live) dt_acc = fmaf(ds, sc, dt_acc);
@@ -405,7 +411,7 @@ __device__ __forceinline__ void lsa_stage_chunk(const bf16_t* __restrict__ src, 
     }
   }
 }
-template <int DH, bool KEYS, bool PLAIN>
+template <int DH, bool KEYS, bool PLAIN, bool BIAS = false>
 __global__ __launch_bounds__(256) void attn_lsa_bwd_mfma_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
                                                                 const bf16_t* __restrict__ d_o, const float* __restrict__ lse,
                                                                 float* __restrict__ dsum, bf16_t* __restrict__ dqkv,
@@ -489,7 +495,8 @@ __global__ __launch_bounds__(256) void attn_lsa_bwd_mfma_kernel(const bf16_t* __
       for (int r = 0; r < 4; ++r) {
         const int row = r0 + 4 * lg + r;
         const bool live = row < n && c < n && (PLAIN || row != c);
-        const float sc = sa[r] * et;
+        float sc = sa[r] * et;
+        if (BIAS && live) sc += KEYS ? temperature[(int64_t)c * n + row] : temperature[(int64_t)row * n + c];   // bias[query][key]
         const float p = live ? expf(sc - (KEYS ? lc : lrow[r])) : 0.f;
         const float ds = p * (sb[r] - (KEYS ? Dc : Drow[r]));
         if (!KEYS && !PLAIN && live) dt_acc = fmaf(ds, sc, dt_acc);
@@ -534,20 +541,20 @@ __global__ __launch_bounds__(256) void attn_lsa_bwd_mfma_kernel(const bf16_t* __
       dt_part[((int64_t)bi * h + hi) * gridDim.x + blockIdx.x] = ((dt_wave[0] + dt_wave[1]) + dt_wave[2]) + dt_wave[3];
   }
 }
-template <int DH, bool KEYS, bool PLAIN>
+template <int DH, bool KEYS, bool PLAIN, bool BIAS = false>
 void lsa_bwd_mfma_launch(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o, const float* lse, float* dsum, bf16_t* dqkv, int b, int n, int h,
                          const float* t, float scale, float* part, hipStream_t s) {
   constexpr int DHP = DH < 32 ? 32 : DH, KP = DHP + 8, TP = LSA_NC + 8;
   const size_t lds = ((size_t)2 * LSA_NC * KP + (size_t)(KEYS ? 2 : 1) * DH * TP + (size_t)LSA_WAVES * (KEYS ? 2 : 1) * 16 * TP) * 2;
-  auto kern = attn_lsa_bwd_mfma_kernel<DH, KEYS, PLAIN>;
+  auto kern = attn_lsa_bwd_mfma_kernel<DH, KEYS, PLAIN, BIAS>;
   vitx_set_max_smem((const void*)kern, LSA_LDS_MAX);
   hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, d_o, lse, dsum, dqkv, t, scale, part, n, h);
 }
-template <int DH, bool PLAIN>
+template <int DH, bool PLAIN, bool BIAS = false>
 void lsa_bwd_mfma_dh(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o, const float* lse, float* dsum, bf16_t* dqkv, int b, int n, int h,
                      const float* t, float scale, float* part, hipStream_t s) {
-  lsa_bwd_mfma_launch<DH, false, PLAIN>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);   // (first: it writes the row sums the key pass reads)
-  lsa_bwd_mfma_launch<DH, true, PLAIN>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
+  lsa_bwd_mfma_launch<DH, false, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);   // (first: it writes the row sums the key pass reads)
+  lsa_bwd_mfma_launch<DH, true, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
 }
 
 // second pass of the temperature gradient: one workgroup, every thread a fixed strided share, then a fixed tree
@@ -571,17 +578,17 @@ template <typename T, int DH> size_t lsa_bwd_lds(int n, int R, bool keys) {
   return (((size_t)2 * n * lsa_pitch<T, DH>() * sizeof(T) + 15) & ~(size_t)15) + (size_t)LSA_WAVES * (2 * R * DH + (keys ? 2 : 1) * R * lsa_npad(n)) * 4;
 }
 
-template <typename T, int DH, int R, bool PLAIN>
+template <typename T, int DH, int R, bool PLAIN, bool BIAS = false>
 void lsa_fwd_launch(const T* qkv, T* o, float* lse, int b, int n, int h, const float* t, float scale, size_t lds, hipStream_t s) {
-  auto kern = attn_lsa_fwd_kernel<T, DH, R, PLAIN>;
+  auto kern = attn_lsa_fwd_kernel<T, DH, R, PLAIN, BIAS>;
   vitx_set_max_smem((const void*)kern, LSA_LDS_MAX);
   hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, lse, t, scale, n, h);
 }
-template <typename T, int DH, bool PLAIN>
+template <typename T, int DH, bool PLAIN, bool BIAS = false>
 void lsa_fwd_dh(const T* qkv, T* o, float* lse, int b, int n, int h, const float* t, float scale, hipStream_t s) {
-  if (lsa_fwd_lds<T, DH>(n, 4) <= (size_t)LSA_LDS_MAX) lsa_fwd_launch<T, DH, 4, PLAIN>(qkv, o, lse, b, n, h, t, scale, lsa_fwd_lds<T, DH>(n, 4), s);
-  else if (lsa_fwd_lds<T, DH>(n, 2) <= (size_t)LSA_LDS_MAX) lsa_fwd_launch<T, DH, 2, PLAIN>(qkv, o, lse, b, n, h, t, scale, lsa_fwd_lds<T, DH>(n, 2), s);
-  else lsa_fwd_launch<T, DH, 1, PLAIN>(qkv, o, lse, b, n, h, t, scale, lsa_fwd_lds<T, DH>(n, 1), s);
+  if (lsa_fwd_lds<T, DH>(n, 4) <= (size_t)LSA_LDS_MAX) lsa_fwd_launch<T, DH, 4, PLAIN, BIAS>(qkv, o, lse, b, n, h, t, scale, lsa_fwd_lds<T, DH>(n, 4), s);
+  else if (lsa_fwd_lds<T, DH>(n, 2) <= (size_t)LSA_LDS_MAX) lsa_fwd_launch<T, DH, 2, PLAIN, BIAS>(qkv, o, lse, b, n, h, t, scale, lsa_fwd_lds<T, DH>(n, 2), s);
+  else lsa_fwd_launch<T, DH, 1, PLAIN, BIAS>(qkv, o, lse, b, n, h, t, scale, lsa_fwd_lds<T, DH>(n, 1), s);
 }
 template <typename T>
 void lsa_fwd_t(const T* qkv, T* o, float* lse, int b, int n, int h, int dh, const float* t, hipStream_t s) {
@@ -590,27 +597,27 @@ void lsa_fwd_t(const T* qkv, T* o, float* lse, int b, int n, int h, int dh, cons
   else lsa_fwd_dh<T, 16, false>(qkv, o, lse, b, n, h, t, 0.f, s);
 }
 
-template <typename T, int DH, int R, bool KEYS, bool PLAIN>
+template <typename T, int DH, int R, bool KEYS, bool PLAIN, bool BIAS = false>
 void lsa_bwd_launch(const T* qkv, const T* o, const T* d_o, const float* lse, float* dsum, T* dqkv, int b, int n, int h, const float* t, float scale,
                     float* part, hipStream_t s) {
-  auto kern = attn_lsa_bwd_kernel<T, DH, R, KEYS, PLAIN>;
+  auto kern = attn_lsa_bwd_kernel<T, DH, R, KEYS, PLAIN, BIAS>;
   vitx_set_max_smem((const void*)kern, LSA_LDS_MAX);
   const size_t lds = lsa_bwd_lds<T, DH>(n, R, KEYS);
   hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, d_o, lse, dsum, dqkv, t, scale, part, n, h);
 }
 // each pass with the most rows per wave whose LDS rows still fit beside the staged operands
-template <typename T, int DH, bool KEYS, bool PLAIN>
+template <typename T, int DH, bool KEYS, bool PLAIN, bool BIAS = false>
 void lsa_bwd_pass(const T* qkv, const T* o, const T* d_o, const float* lse, float* dsum, T* dqkv, int b, int n, int h, const float* t, float scale,
                   float* part, hipStream_t s) {
-  if (lsa_bwd_lds<T, DH>(n, 4, KEYS) <= (size_t)LSA_LDS_MAX) lsa_bwd_launch<T, DH, 4, KEYS, PLAIN>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
-  else if (lsa_bwd_lds<T, DH>(n, 2, KEYS) <= (size_t)LSA_LDS_MAX) lsa_bwd_launch<T, DH, 2, KEYS, PLAIN>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
-  else lsa_bwd_launch<T, DH, 1, KEYS, PLAIN>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
+  if (lsa_bwd_lds<T, DH>(n, 4, KEYS) <= (size_t)LSA_LDS_MAX) lsa_bwd_launch<T, DH, 4, KEYS, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
+  else if (lsa_bwd_lds<T, DH>(n, 2, KEYS) <= (size_t)LSA_LDS_MAX) lsa_bwd_launch<T, DH, 2, KEYS, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
+  else lsa_bwd_launch<T, DH, 1, KEYS, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
 }
-template <typename T, int DH, bool PLAIN>
+template <typename T, int DH, bool PLAIN, bool BIAS = false>
 void lsa_bwd_dh(const T* qkv, const T* o, const T* d_o, const float* lse, float* dsum, T* dqkv, int b, int n, int h, const float* t, float scale,
                 float* part, hipStream_t s) {
-  lsa_bwd_pass<T, DH, false, PLAIN>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);   // (first: it writes the row sums the key pass reads)
-  lsa_bwd_pass<T, DH, true, PLAIN>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
+  lsa_bwd_pass<T, DH, false, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);   // (first: it writes the row sums the key pass reads)
+  lsa_bwd_pass<T, DH, true, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
 }
 template <typename T>
 void lsa_bwd_t(const T* qkv, const T* o, const T* d_o, const float* lse, float* dsum, T* dqkv, int b, int n, int h, int dh, const float* t, float* part,
@@ -648,9 +655,18 @@ void launch_attn_lsa_bwd(const void* qkv, const void* o, const void* d_o, const 
 
 // Plain small-head attention (nest.py:93-109, on a vitx_config.nest_block engine): the kernels above in their PLAIN mode -- no diagonal mask, the scale
 // dim_head^-0.5 passed by value, no temperature partials and no second pass, n >= 1.  dim_head 64 keeps attn_bf16 / attn_x3.
+// BIAS (a third compile-time mode on top of PLAIN, dim_head 32): an additive fp32 [n, n] bias on the scaled scores, forward and where both
+// backward passes recompute P.  The pointer rides in the kernels' `temperature` argument, which PLAIN never reads, so that the argument lists --
+// and the code of the PLAIN and LSA instantiations -- stay what they were.
 bool attn_small_supported(int n, int dim_head) { return (dim_head == 16 || dim_head == 32) && n >= 1 && n <= LSA_N_MAX; }
 
-void launch_attn_small_fwd(const void* qkv, void* o, float* lse, int is_bf16, int b, int n, int h, int dim_head, float scale, hipStream_t s) {
+void launch_attn_small_fwd(const void* qkv, void* o, float* lse, int is_bf16, int b, int n, int h, int dim_head, float scale, hipStream_t s,
+                           const float* bias) {
+  if (bias) {   // BIAS mode (crossformer.py:156-168): s = scale q k^T + bias[i][j]; dim_head 32 only; the bias travels in the temperature slot
+    if (is_bf16) lsa_fwd_mfma_launch<32, true, true>((const bf16_t*)qkv, (bf16_t*)o, lse, b, n, h, bias, scale, s);
+    else lsa_fwd_dh<float, 32, true, true>((const float*)qkv, (float*)o, lse, b, n, h, bias, scale, s);
+    return;
+  }
   if (is_bf16) {
     if (dim_head == 32) lsa_fwd_mfma_launch<32, true>((const bf16_t*)qkv, (bf16_t*)o, lse, b, n, h, nullptr, scale, s);
     else lsa_fwd_mfma_launch<16, true>((const bf16_t*)qkv, (bf16_t*)o, lse, b, n, h, nullptr, scale, s);
@@ -659,7 +675,12 @@ void launch_attn_small_fwd(const void* qkv, void* o, float* lse, int is_bf16, in
 }
 
 void launch_attn_small_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, float* dsum_ws, void* dqkv, int is_bf16, int b, int n, int h,
-                           int dim_head, float scale, hipStream_t s) {
+                           int dim_head, float scale, hipStream_t s, const float* bias) {
+  if (bias) {   // the bias is a constant of the step: it is needed only to recompute P
+    if (is_bf16) lsa_bwd_mfma_dh<32, true, true>((const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)d_o, lse, dsum_ws, (bf16_t*)dqkv, b, n, h, bias, scale, nullptr, s);
+    else lsa_bwd_dh<float, 32, true, true>((const float*)qkv, (const float*)o, (const float*)d_o, lse, dsum_ws, (float*)dqkv, b, n, h, bias, scale, nullptr, s);
+    return;
+  }
   if (is_bf16) {
     const bf16_t *q_ = (const bf16_t*)qkv, *o_ = (const bf16_t*)o, *do_ = (const bf16_t*)d_o;
     if (dim_head == 32) lsa_bwd_mfma_dh<32, true>(q_, o_, do_, lse, dsum_ws, (bf16_t*)dqkv, b, n, h, nullptr, scale, nullptr, s);

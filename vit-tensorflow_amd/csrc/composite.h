@@ -1,4 +1,4 @@
-// Host toolkit of the seven composite models (mim.hip, distill.hip, cross_vit.hip, cct.hip, nest.hip, twins.hip, cvt.hip): a C-ABI handle that
+// Host toolkit of the eight composite models (mim.hip, distill.hip, cross_vit.hip, cct.hip, nest.hip, twins.hip, cvt.hip, crossformer.hip): a C-ABI handle that
 // owns a public parameter / gradient arena in its own table order and drives one or more ViT engines.  Here: error plumbing, TableBuilder,
 // DevicePool, the Dense products, the table / blob exports, the arena maps (ArenaMap, add_arena_map, copy_maps), the profiler scope and the
 // begin / end bodies over a handle's engines, and the bodies of the create / host forward / host backward / read exports.  Everything here is

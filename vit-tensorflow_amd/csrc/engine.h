@@ -206,6 +206,11 @@ struct vitx_engine {
   float *cv_dq = nullptr, *cv_dkv = nullptr, *cv_ws = nullptr;
   float bn_eps = 1e-5f;
   bool bn_inference = false;         // BatchNormalization on the moving statistics of the table (forward only)
+  // nest_block handles: one fp32 [attn_bias_n, attn_bias_n] device buffer per block, added to the scaled attention scores (crossformer.py:165);
+  // crossformer.hip sets them after engine_create and owns the buffers.  Empty: no bias, every other handle.
+  std::vector<const float*> attn_bias;
+  int attn_bias_n = 0;
+  bool window_attn = false;   // biased handles, bf16 mode, n <= 64: the one-wave-per-window kernels (attn_window.hip); crossformer.hip sets it per handle
   void* zero_page = nullptr;         // 256 B of zeros (source of the padded rows in the attention DMA staging)
   float* tmp_f32 = nullptr;          // [mp, max(d, pd)] fp32 scratch (dropout / dimg paths)
   float* loss_rows = nullptr;

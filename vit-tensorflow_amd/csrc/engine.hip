@@ -1031,6 +1031,10 @@ static void attn_generic_bwd(vitx_engine* e, const BlockParams& bp, const AttnVi
 static bool use_small_attn(const vitx_engine* e, int n) {
   return e->cfg.nest_block && !reduced_keys(e->cfg) && e->small_attn && !e->force_generic_attn && attn_small_supported(n, e->cfg.dim_head);
 }
+// biased handles in the bf16 mode: one wave per (window, head) for at most 64 tokens of dim_head 32 (attn_window.hip)
+static bool use_window_attn(const vitx_engine* e, int n) {
+  return e->window_attn && e->bf16 && !e->attn_bias.empty() && !e->force_generic_attn && attn_window_supported(n, e->cfg.dim_head);
+}
 static bool use_fused_attn(const vitx_engine* e, int n) {
   return e->bf16 && e->cfg.variant == VITX_VARIANT_VIT && !reduced_keys(e->cfg) && !e->force_generic_attn && attn_bf16_supported(n, e->cfg.dim_head);
 }
@@ -1205,12 +1209,22 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
     av.ldq = av.ldk = av.ldv = 3 * inner;
     av.qb = av.kb = av.vb = (int64_t)nq * 3 * inner;
   }
+  // biased handles (crossformer.py:165): the BIAS form of the small-head kernels, or nothing -- the materialised path has not learnt the bias
+  const float* attn_bias = e->attn_bias.empty() ? nullptr : e->attn_bias[(size_t)l];
+  if (attn_bias && (nq != e->attn_bias_n || c.dim_head != 32 || !use_small_attn(e, nq))) {
+    err = e->force_generic_attn ? "VITX_GENERIC_ATTN: the materialised attention path has no additive score bias; a biased (CrossFormer) handle runs the small-head kernels only"
+                                : "a biased attention handle needs dim_head 32 and sequences of exactly the bias's n <= 288 tokens";
+    return VITX_ERR_UNSUPPORTED;
+  }
   if (c.small_dataset) {   // LSA (vit_for_small_dataset.py:109-117): learned temperature, masked diagonal
     Prof pr(e, "attn_lsa_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
     launch_attn_lsa_fwd(ba.qkv, ba.o, ba.lse, T, b, nq, c.heads, c.dim_head, e->params + bp.temp, e->stream);
+  } else if (attn_bias && use_window_attn(e, nq)) {   // crossformer.py:156-171, tiny windows
+    Prof pr(e, "attn_window_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
+    launch_attn_window_fwd((const bf16_t*)ba.qkv, (bf16_t*)ba.o, ba.lse, attn_bias, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), e->stream);
   } else if (use_small_attn(e, nq)) {   // nest.py:101-105
     Prof pr(e, "attn_small_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
-    launch_attn_small_fwd(ba.qkv, ba.o, ba.lse, T, b, nq, c.heads, c.dim_head, 1.0f / std::sqrt((float)c.dim_head), e->stream);
+    launch_attn_small_fwd(ba.qkv, ba.o, ba.lse, T, b, nq, c.heads, c.dim_head, 1.0f / std::sqrt((float)c.dim_head), e->stream, attn_bias);
   } else if (use_fused_attn_x3(e, nq)) {
     Prof pr(e, "attn_x3_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
     launch_attn_x3_fwd((const float*)ba.qkv, (float*)ba.o, ba.lse, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), e->stream);
@@ -1673,9 +1687,14 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
       Prof pr(e, "attn_lsa_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
       launch_attn_lsa_bwd(ba.qkv, ba.o, d_o, ba.lse, e->dsum, e->d_qkv, T, b, nq, c.heads, c.dim_head, e->params + bp.temp, e->grads + bp.temp,
                           e->lsa_ws, e->stream);
+    } else if (!e->attn_bias.empty() && use_window_attn(e, nq)) {
+      Prof pr(e, "attn_window_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
+      launch_attn_window_bwd((const bf16_t*)ba.qkv, (const bf16_t*)ba.o, (const bf16_t*)d_o, ba.lse, (bf16_t*)e->d_qkv, e->attn_bias[(size_t)l], b, nq, c.heads,
+                             1.0f / std::sqrt((float)c.dim_head), e->stream);
     } else if (use_small_attn(e, nq)) {
       Prof pr(e, "attn_small_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
-      launch_attn_small_bwd(ba.qkv, ba.o, d_o, ba.lse, e->dsum, e->d_qkv, T, b, nq, c.heads, c.dim_head, 1.0f / std::sqrt((float)c.dim_head), e->stream);
+      launch_attn_small_bwd(ba.qkv, ba.o, d_o, ba.lse, e->dsum, e->d_qkv, T, b, nq, c.heads, c.dim_head, 1.0f / std::sqrt((float)c.dim_head), e->stream,
+                            e->attn_bias.empty() ? nullptr : e->attn_bias[(size_t)l]);
     } else if (use_fused_attn_x3(e, nq)) {
       Prof pr(e, "attn_x3_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
       launch_attn_x3_bwd((const float*)ba.qkv, (const float*)ba.o, (const float*)d_o, ba.lse, (float*)e->d_qkv, b, nq, c.heads,

@@ -108,9 +108,31 @@ void launch_attn_lsa_bwd(const void* qkv, const void* o, const void* d_o, const 
 // plain small-head attention (nest.py:93-109): the same kernels compiled without the diagonal mask and the temperature, softmax scale by value;
 // dim_head in {16, 32}, 1 <= n <= LSA_N_MAX
 bool attn_small_supported(int n, int dim_head);
-void launch_attn_small_fwd(const void* qkv, void* o, float* lse, int is_bf16, int b, int n, int h, int dim_head, float scale, hipStream_t s);
+// bias: optional fp32 [n, n] added to the scaled scores (dim_head 32 only; crossformer.py:165)
+void launch_attn_small_fwd(const void* qkv, void* o, float* lse, int is_bf16, int b, int n, int h, int dim_head, float scale, hipStream_t s,
+                           const float* bias = nullptr);
 void launch_attn_small_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, float* dsum_ws, void* dqkv, int is_bf16, int b, int n, int h,
-                           int dim_head, float scale, hipStream_t s);
+                           int dim_head, float scale, hipStream_t s, const float* bias = nullptr);
+// attn_window.hip -- biased attention of tiny windows (crossformer.py:149-172): bf16 storage, dim_head 32, 1 <= n <= 64; one wave per (sequence, head);
+// s = scale q k^T + bias[n, n] (fp32), softmax, P v on the packed qkv [b, n, 3, h, 32] and its VJP (d(q, k, v) written by the same wave: no workspace)
+bool attn_window_supported(int n, int dim_head);
+void launch_attn_window_fwd(const bf16_t* qkv, bf16_t* o, float* lse, const float* bias, int b, int n, int h, float scale, hipStream_t s);
+void launch_attn_window_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o, const float* lse, bf16_t* dqkv, const float* bias, int b, int n, int h,
+                            float scale, hipStream_t s);
+// crossformer_ops.hip -- CrossFormer (crossformer.py) outside its transformer blocks
+// tokens[(b h w), (l1 l2), c] = x[b, l1 * (H / g) + h, l2 * (W / g) + w, c] ('b (l1 h) (l2 w) d -> (b h w) l1 l2 d', :146) and its inverse (:178);
+// each is the other's VJP
+void launch_cf_to_dilated(const float* x, float* tokens, int b, int H, int W, int g, int c, hipStream_t s);
+void launch_cf_from_dilated(const float* tokens, float* x, int b, int H, int W, int g, int c, hipStream_t s);
+// DynamicPositionBias (:51-71) of one attention on its (2 wsz + 1)^2 positions and the [n, n] gather through rel_pos_indices (:126-131,159-163),
+// fp32 in every compute mode.  t: the 14 dpb tensors of the attention in table order -- (kernel, bias, gamma, beta) x 3, then kernel [d4, 1], bias [1].
+// ws: cf_dpb_ws_elems floats (the network's output per position); bias: [wsz^2, wsz^2].
+struct CfDpbParams { const float* t[14]; };
+int64_t cf_dpb_ws_elems(int wsz);
+void launch_cf_dpb_bias(const CfDpbParams& p, int d4, int wsz, float* ws, float* bias, hipStream_t s);
+// dst[r, col0 : col0 + w] = src[r, 0 : w] (put) / dst[r, 0 : w] = src[r, col0 : col0 + w] (get): one scale's column block of the stage input
+void launch_cf_cols_put(const float* src, float* dst, int64_t rows, int w, int ld, int col0, hipStream_t s);
+void launch_cf_cols_get(const float* src, float* dst, int64_t rows, int w, int ld, int col0, hipStream_t s);
 
 // ---------------------------------------------------------------- spt.hip
 // shifted patch tokenization (vit_for_small_dataset.py:15-47,142-157): NHWC image -> LayerNorm'ed rows [b * np, 5 p p C] of the image concatenated

@@ -1,7 +1,7 @@
 """What every model object over a native handle shares: the Keras-like weights surface over one host blob in the C library's table order
 (`ParamBlob`: every model, MIM and distill among them), and the Python front of a composite model created from a config -- a C-ABI handle
 that owns its parameter / gradient arenas and drives ViT engines (`NativeComposite`: CrossViT, CCT, NesT; `ImageSizedComposite`: TwinsSVT,
-CvT).  NativeComposite holds the keyword extras, the seeded Keras initialisers, handle management, the forward / backward / read calls, the
+CvT, CrossFormer).  NativeComposite holds the keyword extras, the seeded Keras initialisers, handle management, the forward / backward / read calls, the
 profiler and the refusals.  A new composite starts from here and from csrc/composite.h.  No arithmetic here."""
 from __future__ import annotations
 
@@ -290,7 +290,7 @@ class NativeComposite(ParamBlob):
 
 
 class ImageSizedComposite(NativeComposite):
-    """A composite whose reference constructor takes no image size and none of whose parameters depends on one (TwinsSVT, CvT): the handle is
+    """A composite whose reference constructor takes no image size and none of whose parameters depends on one (TwinsSVT, CvT, CrossFormer): the handle is
     created at the first call from the image's H x W (cfg.image_h / image_w), and again, weights kept, when H x W changes or a larger batch
     arrives.  `_check_image(H, W)` raises ValueError for a size the model cannot take."""
 

@@ -127,6 +127,19 @@ class CvTConfig(C.Structure):
     ]
 
 
+CF_MAX_SCALES = 8
+
+
+class CrossFormerConfig(C.Structure):
+    _fields_ = [
+        ("image_h", C.c_int32), ("image_w", C.c_int32), ("num_classes", C.c_int32),
+        ("dim", C.c_int32 * 4), ("depth", C.c_int32 * 4), ("global_window_size", C.c_int32 * 4), ("local_window_size", C.c_int32 * 4),
+        ("n_kernels", C.c_int32 * 4), ("kernel_sizes", (C.c_int32 * CF_MAX_SCALES) * 4), ("strides", C.c_int32 * 4),
+        ("ln_eps", C.c_float), ("compute", C.c_int32), ("max_batch", C.c_int32), ("device_id", C.c_int32),
+        ("window_attn", C.c_int32), ("reserved", C.c_int32 * 7),
+    ]
+
+
 class CrossViTConfig(C.Structure):
     _fields_ = [
         ("image_size", C.c_int32), ("num_classes", C.c_int32), ("sm_dim", C.c_int32), ("lg_dim", C.c_int32),
@@ -327,6 +340,26 @@ SYMBOLS: List[Tuple[str, object, list]] = [
     ("vitx_cvt_profile_begin", C.c_int32, [C.c_void_p]),
     ("vitx_cvt_profile_end", C.c_int32, [C.c_void_p, _P(KernelStat), C.c_int32, _P(C.c_int32)]),
     ("vitx_cvt_read", C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, _P(C.c_int64)]),
+    ("vitx_crossformer_param_table_size", C.c_int32, [_P(CrossFormerConfig), _P(C.c_int64), _P(C.c_int64)]),
+    ("vitx_crossformer_param_table_entry", C.c_int32,
+     [_P(CrossFormerConfig), C.c_int64, C.c_char_p, C.c_int32, _P(C.c_int64), _P(C.c_int32), _P(C.c_int64)]),
+    ("vitx_crossformer_create", C.c_int32, [_P(CrossFormerConfig), _P(C.c_void_p)]),
+    ("vitx_crossformer_destroy", C.c_int32, [C.c_void_p]),
+    ("vitx_crossformer_set_params", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_crossformer_get_params", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_crossformer_get_grads", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_crossformer_params_dev", C.c_int32, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)]),
+    ("vitx_crossformer_grads_dev", C.c_int32, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)]),
+    ("vitx_crossformer_params_changed", C.c_int32, [C.c_void_p]),
+    ("vitx_crossformer_forward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("vitx_crossformer_forward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("vitx_crossformer_backward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("vitx_crossformer_backward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("vitx_crossformer_profile_begin", C.c_int32, [C.c_void_p]),
+    ("vitx_crossformer_profile_end", C.c_int32, [C.c_void_p, _P(KernelStat), C.c_int32, _P(C.c_int32)]),
+    ("vitx_crossformer_read", C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, _P(C.c_int64)]),
+    ("vitx_crossformer_partition", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 6),
+    ("vitx_crossformer_window_attn", C.c_int32, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_float, C.c_int32] + [C.c_void_p] * 3),
 ]
 
 _lib = None
@@ -398,6 +431,11 @@ def twins_param_table(cfg: TwinsConfig):
 def cvt_param_table(cfg: CvTConfig):
     """[(name, shape, offset)] of CvT's variables from the C library (host-only call; no GPU needed)."""
     return table_of("vitx_cvt", C.byref(cfg))
+
+
+def crossformer_param_table(cfg: CrossFormerConfig):
+    """[(name, shape, offset)] of CrossFormer's variables from the C library (host-only call; no GPU needed)."""
+    return table_of("vitx_crossformer", C.byref(cfg))
 
 
 def mim_param_table(handle, prefix="vitx_mim"):
