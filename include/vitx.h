@@ -168,6 +168,16 @@ int32_t vitx_forward_dev(vitx_handle h, const float* img_dev, int32_t b, int32_t
  * b; fills the gradient arena (overwrites, no accumulation).  dimg may be NULL (TF does not
  * differentiate w.r.t. an un-watched image). */
 int32_t vitx_backward(vitx_handle h, const float* dlogits_host, float* dimg_host_or_null);
+/* Long sequences: Attention.call (vit.py:73-82) past the 288 tokens the fused bf16 attention kernels hold in LDS, e.g. ViT-B/16 at 384 px (577
+ * tokens).  on != 0: such a sequence runs the streamed-key kernels (csrc/attn_stream.hip: K / V chunks through an LDS ring, online softmax, the
+ * [b, heads, n, n] scores never in HBM, no score workspace) instead of the materialised path; at n <= 288, or under VITX_GENERIC_ATTN, nothing
+ * changes.  0 (the default of every new handle) = as before.  vitx_config has no spare word, hence a setter.  Call it between steps, at any time:
+ * after a forward with training == 0 (a step of its own: a forward-only caller may switch whenever it likes) and after any backward.  Between a
+ * forward with training != 0 and its backward it returns VITX_ERR_STATE.  A backward always takes the path its forward took.  Whatever
+ * `on` is, a handle that can never take the path -- FP32_PARITY or BF16X3 compute, a variant other than VITX_VARIANT_VIT, dim_head != 64,
+ * small_dataset / cct_block / nest_block -- returns VITX_ERR_UNSUPPORTED with the reason in vitx_last_error().  Sequence bounds: b * heads <= 65535
+ * and n * 3 * heads * 64 < 2^30 elements per image, else the forward returns VITX_ERR_UNSUPPORTED. */
+int32_t vitx_set_long_attn(vitx_handle h, int32_t on);
 /* Forward from caller-supplied patch rows [b, np, patch_dim] (fp32) in place of the image + Rearrange: the first layer(s) of T2T-ViT's
  * patch_embedding are a tokenizer pipeline (t2t.py:59-77) whose output feeds the same Dense, cls / position rows, transformer and head
  * (t2t.py:99-121).  A backward after it returns d(patches) [b, np, patch_dim] through the dimg argument. */

@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libvitx.so")
-SOURCES = ["env.hip", "elementwise.hip", "gemm_generic.hip", "gemm_f32_mfma.hip", "gemm_bf16x3.hip", "gemm_bf16.hip", "gemm_bf16_pipe.hip", "gemm_bf16_tn.hip", "attn_bf16.hip", "attn_x3.hip", "attn_generic.hip", "attn_lsa.hip", "attn_fewkey.hip", "attn_window.hip", "spt.hip", "attn_bgemm_mfma.hip", "attn_headchain.hip", "attn_deepvit_fused.hip", "attn_cait_fused.hip", "mim_ops.hip", "mim.hip", "distill.hip", "cross_vit.hip", "cct_tok.hip", "cct.hip", "nest_ops.hip", "nest.hip", "twins_ops.hip", "twins.hip", "cvt_ops.hip", "cvt.hip", "crossformer_ops.hip", "crossformer.hip", "comm.hip", "engine.hip", "capi.hip"]
+SOURCES = ["env.hip", "elementwise.hip", "gemm_generic.hip", "gemm_f32_mfma.hip", "gemm_bf16x3.hip", "gemm_bf16.hip", "gemm_bf16_pipe.hip", "gemm_bf16_tn.hip", "attn_bf16.hip", "attn_stream.hip", "attn_x3.hip", "attn_generic.hip", "attn_lsa.hip", "attn_fewkey.hip", "attn_window.hip", "spt.hip", "attn_bgemm_mfma.hip", "attn_headchain.hip", "attn_deepvit_fused.hip", "attn_cait_fused.hip", "mim_ops.hip", "mim.hip", "distill.hip", "cross_vit.hip", "cct_tok.hip", "cct.hip", "nest_ops.hip", "nest.hip", "twins_ops.hip", "twins.hip", "cvt_ops.hip", "cvt.hip", "crossformer_ops.hip", "crossformer.hip", "comm.hip", "engine.hip", "capi.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # per-source additions.  attn_bf16.hip / attn_x3.hip: the running row maxima come straight out of MFMA accumulators; with NaNs honoured every fmaxf first
@@ -50,7 +50,8 @@ def flags_id() -> str:
 # hipcc does not model M0 across asm statements (an "m0" clobber only draws `inline asm clobber list contains reserved registers`), so the
 # guarantee is checked on the ISA of EVERY build instead of trusted: no M0 write but the DMA statements' own, no compiler vmcnt wait and no
 # scratch access inside a K loop (tools/isa_check.py).  A compiler that breaks either fails the build here, not a run on the GPU.
-ISA_CHECKED = ["gemm_bf16_pipe.hip", "gemm_bf16_tn.hip"]
+# attn_stream.hip: the chunk loops of the streamed attention kernels use the same asm DMA; their gate counts waits over the whole loop (check_stream).
+ISA_CHECKED = ["gemm_bf16_pipe.hip", "gemm_bf16_tn.hip", "attn_stream.hip"]
 
 
 def _isa_gate(objs) -> None:
@@ -67,9 +68,12 @@ def _isa_gate(objs) -> None:
             continue
         bad = []
         for name, body in mod.kernels(mod.disassemble(obj)):
-            if "nt_pipe_kernel" not in name and "gemm_bf16_tn_kernel" not in name:
+            if "attn_stream" in name:
+                r = mod.check_stream(name, body)
+            elif "nt_pipe_kernel" not in name and "gemm_bf16_tn_kernel" not in name:
                 continue
-            r = mod.check(name, body)
+            else:
+                r = mod.check(name, body)
             if r is not None and not r[0]:
                 bad.append(r[1])
         if bad:

@@ -161,6 +161,23 @@ int32_t vitx_forward_dev(vitx_handle h, const float* img_dev, int32_t b, int32_t
   CAPI_CATCH
 }
 
+int32_t vitx_set_long_attn(vitx_handle h, int32_t on) {
+  if (!h) return fail(VITX_ERR_INVALID, "null handle");
+  const vitx_config& c = h->cfg;
+  const char* why = nullptr;
+  if (c.compute == VITX_COMPUTE_FP32_PARITY) why = "the streamed attention kernels are bf16 only (this handle computes in fp32)";
+  else if (c.compute == VITX_COMPUTE_BF16X3) why = "the streamed attention kernels are bf16 only (this handle computes in bf16x3)";
+  else if (c.variant != VITX_VARIANT_VIT) why = "ViT handles only (DeepViT, CaiT and the PatchMerger ViT keep their own attention paths)";
+  else if (c.dim_head != 64) why = "dim_head must be 64";
+  else if (c.small_dataset) why = "not for small_dataset (LSA) handles";
+  else if (c.cct_block) why = "not for cct_block handles";
+  else if (c.nest_block) why = "not for nest_block handles (global_k and conv_proj ones included)";
+  if (why) return fail(VITX_ERR_UNSUPPORTED, std::string("set_long_attn: ") + why);
+  if (h->bwd_pending) return fail(VITX_ERR_STATE, "set_long_attn: a training forward is waiting for its backward; switch between steps");
+  h->long_attn = on != 0;
+  return VITX_OK;
+}
+
 int32_t vitx_set_patch_input(vitx_handle h, int32_t np) {
   if (!h) return fail(VITX_ERR_INVALID, "null handle");
   if (np < 0 || np > h->np_max) return fail(VITX_ERR_INVALID, "set_patch_input: np must be in [0, num_patches]");

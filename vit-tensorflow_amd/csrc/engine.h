@@ -94,6 +94,7 @@ struct BlockActs {
   int sc_pi = 0;                    // index of the tensor that multiplies V
   bool sc_no_mixed = false;         // kept by the one-kernel DeepViT forward: sc_keep[1] (the mixed scores) was not written
   bool sc_a2_bf16 = false;   // sc_keep[2] holds bf16 [nq][round_up(nk, 8)] planes (one-kernel forward with the one-kernel backward as its reader)
+  bool attn_streamed = false;       // the last forward of this block ran the streamed-key attention (attn_stream.hip): its backward does too
   int par_first = 0, par_last = 0;   // backward order inside a group of parallel half-blocks: first / last one processed (1 + 1 = alone)
 };
 
@@ -254,6 +255,8 @@ struct vitx_engine {
   bool force_generic_gemm = false, force_generic_attn = false, wgrad_via_transpose = true;
   bool fewkey_attn = true;  // global_k handles, bf16 mode: the few-key attention kernels (attn_fewkey.hip) where they apply; twins.hip sets it per handle
   bool manykey_attn = true; // conv_proj handles, bf16 mode: the many-key attention kernels (64 < keys <= MANYKEY_MAX); cvt.hip sets it per handle
+  bool long_attn = false;   // vitx_set_long_attn: past 288 tokens the streamed-key attention kernels (attn_stream.hip) instead of the materialised path
+  bool bwd_pending = false; // a training forward (training != 0) has run and no backward has finished since (vitx_set_long_attn refuses then)
   bool small_attn = true;   // nest_block handles: plain small-head attention kernels where they apply; nest.hip sets it per handle (vitx_nest_config.small_attn)
   int gemm_kernel = 0;
   int gemm_tail = 0;      // forced tail variant (VITX_GEMM_TAIL_KERNEL; only with a forced main variant)

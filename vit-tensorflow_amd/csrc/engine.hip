@@ -1038,6 +1038,13 @@ static bool use_window_attn(const vitx_engine* e, int n) {
 static bool use_fused_attn(const vitx_engine* e, int n) {
   return e->bf16 && e->cfg.variant == VITX_VARIANT_VIT && !reduced_keys(e->cfg) && !e->force_generic_attn && attn_bf16_supported(n, e->cfg.dim_head);
 }
+// long_attn handles (vitx_set_long_attn) past the 288 tokens of the kernels above: the streamed-key kernels (attn_stream.hip), which save what the
+// fused path saves (qkv, o, lse) and touch no score workspace.  At n <= 288 such a handle runs the fused kernels as every other one.
+static bool use_stream_attn(const vitx_engine* e, int n) {
+  const vitx_config& c = e->cfg;
+  return e->long_attn && e->bf16 && c.variant == VITX_VARIANT_VIT && !reduced_keys(c) && !c.small_dataset && !c.cct_block && !c.nest_block &&
+         !e->force_generic_attn && attn_stream_supported(n, c.dim_head);
+}
 // global_k and conv_proj handles in the bf16 mode: the few-key kernels (attn_fewkey.hip) for at most 64 keys of dim_head 64
 static bool use_fewkey_attn(const vitx_engine* e, int b, int nq, int nk) {
   return reduced_keys(e->cfg) && e->bf16 && e->fewkey_attn && !e->force_generic_attn && (int64_t)b * e->cfg.heads <= 65535 &&
@@ -1216,6 +1223,7 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
                                 : "a biased attention handle needs dim_head 32 and sequences of exactly the bias's n <= 288 tokens";
     return VITX_ERR_UNSUPPORTED;
   }
+  ba.attn_streamed = false;
   if (c.small_dataset) {   // LSA (vit_for_small_dataset.py:109-117): learned temperature, masked diagonal
     Prof pr(e, "attn_lsa_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
     launch_attn_lsa_fwd(ba.qkv, ba.o, ba.lse, T, b, nq, c.heads, c.dim_head, e->params + bp.temp, e->stream);
@@ -1234,6 +1242,11 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
     Prof pr(e, "attn_bf16_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head * live, (double)rows * inner * (2 + 2 * live) * esz);
     launch_attn_bf16_fwd((const bf16_t*)ba.qkv, (bf16_t*)ba.o, ba.lse, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), (const bf16_t*)e->zero_page, (e->reverse_mask >> 2) & 1, e->stream,
                          cls_rows ? 1 : 0);
+  } else if (use_stream_attn(e, nq)) {
+    if (!attn_stream_fits(b, nq, c.heads)) { err = "long_attn: the streamed attention kernels take b * heads <= 65535 and n * 3 * heads * 64 < 2^30 elements per image"; return VITX_ERR_UNSUPPORTED; }
+    Prof pr(e, "attn_stream_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
+    ba.attn_streamed = true;
+    launch_attn_stream_fwd((const bf16_t*)ba.qkv, (bf16_t*)ba.o, ba.lse, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), e->stream);
   } else if (use_fewkey_attn(e, b, nq, nk)) {   // twins_svt.py:184-187
     Prof pr(e, "attn_fewkey_fwd", 4.0 * b * c.heads * (double)nq * nk * c.dim_head, ((double)rows * inner * 2 + (double)b * nk * 2 * inner) * esz);
     launch_attn_fewkey_fwd((const bf16_t*)ba.q, (const bf16_t*)ba.kv, (bf16_t*)ba.o, ba.lse, b, nq, nk, c.heads, inner, 2 * inner, inner,
@@ -1705,6 +1718,10 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
       Prof pr(e, "attn_bf16_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head * live, (double)rows * inner * (5 + 3 * live) * esz);
       launch_attn_bf16_bwd((const bf16_t*)ba.qkv, (const bf16_t*)ba.o, (const bf16_t*)d_o, ba.lse, e->dsum, (bf16_t*)e->d_qkv, b, nq,
                            c.heads, 1.0f / std::sqrt((float)c.dim_head), (const bf16_t*)e->zero_page, e->stream, cls_rows ? 1 : 0);
+    } else if (ba.attn_streamed) {   // the path this block's forward took (the flag may have been switched since: the saved state decides)
+      Prof pr(e, "attn_stream_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
+      launch_attn_stream_bwd((const bf16_t*)ba.qkv, (const bf16_t*)ba.o, (const bf16_t*)d_o, ba.lse, e->dsum, (bf16_t*)e->d_qkv, b, nq, c.heads,
+                             1.0f / std::sqrt((float)c.dim_head), e->stream);
     } else {
       int rc = ensure_scores(e, 4, (int64_t)b * c.heads * nq * round_up(nk, 4), err);
       if (rc != VITX_OK) return rc;
@@ -2460,6 +2477,7 @@ int engine_forward(vitx_engine* e, const float* img_dev, int b, int H, int W, in
   e->last_extra = extra;
   e->last_cls_only = cls_rows;
   e->have_fwd = true;
+  e->bwd_pending = training != 0;   // an inference forward is a step of its own (a backward after it still follows the blocks' recorded paths)
   e->have_tf = false;
   e->last_b = b; e->last_np = np; e->last_ntok = ntok; e->last_H = H; e->last_W = W; e->last_training = training; e->last_seed = seed;
   return VITX_OK;
@@ -2674,6 +2692,7 @@ int engine_transformer_forward(vitx_engine* e, const float* tokens_dev, int b, i
   HIPCHK(hipMemcpyAsync(out_dev, s0.ba[(size_t)l1 - 1].x_out, bytes, hipMemcpyDeviceToDevice, e->stream));
   e->have_fwd = false; e->last_cls_only = false;   // saved activations no longer describe a full model forward
   e->have_tf = true; e->tf_b = b; e->tf_n = n; e->tf_drop = drop; e->tf_seed = seed;
+  e->bwd_pending = training != 0;   // an inference forward is a step of its own (a backward after it still follows the blocks' recorded paths)
   e->last_training = 0;
   return VITX_OK;
 }
@@ -2696,6 +2715,7 @@ int engine_transformer_backward(vitx_engine* e, const float* dout_dev, float* dt
   if (l1 == s0.depth) { Prof pr(e, "fill_zero", 0, (double)e->n_arena * 4); launch_fill_zero(e->grads, (int64_t)e->n_arena * 4, e->stream); }
   if (l0 == l1) {
     if (dtokens_dev && dtokens_dev != dout_dev) HIPCHK(hipMemcpyAsync(dtokens_dev, dout_dev, bytes, hipMemcpyDeviceToDevice, e->stream));
+    if (l0 == 0) e->bwd_pending = false;
     return VITX_OK;
   }
   launch_fill_zero(e->g, (int64_t)round_up((int64_t)b * n, 256) * d * 4, e->stream);
@@ -2707,6 +2727,7 @@ int engine_transformer_backward(vitx_engine* e, const float* dout_dev, float* dt
   for (int l = l1 - 1; l >= l0; --l)
     if ((rc = block_backward(e, s0, 0, l, b, n, 0, e->tf_drop, e->tf_seed, err, l > l0 ? l - 1 : -1)) != VITX_OK) return rc;
   if (dtokens_dev) HIPCHK(hipMemcpyAsync(dtokens_dev, e->g, bytes, hipMemcpyDeviceToDevice, e->stream));
+  if (l0 == 0) e->bwd_pending = false;   // the last range of the step
   return VITX_OK;
 }
 
@@ -2924,6 +2945,7 @@ int engine_backward(vitx_engine* e, const float* dlogits_dev, float* dimg_dev, s
     }
   }
   report_ready(e, 0, e->stages[0].depth > 0 ? e->stages[0].bp[0].p_begin : e->head_g);
+  e->bwd_pending = false;
   return VITX_OK;
 }
 

@@ -94,6 +94,18 @@ void launch_attn_x3_bwd(const float* qkv, const float* o, const float* d_o, cons
 void launch_attn_bf16_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o, const float* lse, float* dsum_ws,
                           bf16_t* dqkv, int b, int n, int h, float scale, const bf16_t* zero_page, hipStream_t s, int nq_live = 0);
 
+// ---------------------------------------------------------------- attn_stream.hip
+// the same attention for n > 288 tokens: K / V (backward: also Q / dO) chunks of 64 rows streamed through a double-buffered LDS ring, online softmax;
+// same layouts and the same meaning of lse.  LDS per workgroup does not depend on n.  Upper bounds: n <= ATTN_STREAM_MAX_N (supported), and per launch
+// b * h <= 65535 with n * 3 * h * 64 < 2^30 elements (31-bit byte offsets) per image (fits); lse and dsum_ws hold b * h * n floats.  No allocation, no host synchronisation.
+constexpr int ATTN_STREAM_MAX_N = 1 << 20;
+bool attn_stream_supported(int n, int dim_head);
+bool attn_stream_fits(int b, int n, int h);
+void launch_attn_stream_fwd(const bf16_t* qkv, bf16_t* o, float* lse, int b, int n, int h, float scale, hipStream_t s);
+// d(q) (which also writes D = rowsum(dO * O) to dsum_ws), then d(k) / d(v); every row < n of dqkv [b, n, 3, h, 64] is written
+void launch_attn_stream_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o, const float* lse, float* dsum_ws, bf16_t* dqkv, int b, int n, int h,
+                            float scale, hipStream_t s);
+
 // ---------------------------------------------------------------- attn_lsa.hip
 // locality self-attention (vit_for_small_dataset.py:88-121) on packed qkv [b, n, 3, h, dh] (fp32 storage: exact fp32 FMA; bf16 storage: every product
 // on the bf16 matrix pipe with P / dS rounded to bf16 in front of the second products, fp32 softmax and accumulation): scores scaled by

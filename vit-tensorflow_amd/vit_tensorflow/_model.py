@@ -132,7 +132,7 @@ class VitxModel(ParamBlob):
 
     def _init_common(self, *, image_size, patch_size, num_classes, dim, depth, heads, mlp_dim, pool, dim_head, dropout,
                      emb_dropout, layer_dropout=0.0, cls_depth=0, num_parallel_branches=1, patch_merge_layer=None, patch_merge_num_tokens=8,
-                     small_dataset=0, compute="fp32", max_batch=None, device=0, seed=None, channels=3):
+                     small_dataset=0, compute="fp32", max_batch=None, device=0, seed=None, channels=3, long_attn=False):
         ih, iw = pair(image_size)
         ph, pw = pair(patch_size)
         assert ih % ph == 0 and iw % pw == 0, 'Image dimensions must be divisible by the patch size.'
@@ -159,6 +159,10 @@ class VitxModel(ParamBlob):
         cfg.device_id = int(device)
         self._cfg = cfg
         self.compute = compute
+        self._long_attn = False
+        if long_attn:
+            self._check_long_attn()   # ValueError here, before any device is touched
+            self._long_attn = True
         self._handle: Optional[C.c_void_p] = None
         self._handle_gen = 0                           # bumped whenever the device plan is (re)built: wrappers hanging off it follow
         self._borrowed = False                         # True: the handle belongs to a wrapper object (MAE's decoder)
@@ -195,6 +199,40 @@ class VitxModel(ParamBlob):
                 v = np.zeros(n)
             self._blob[off:off + n] = v.astype(np.float32)
 
+    # ---- long sequences (vitx_set_long_attn): past 288 tokens the streamed-key attention kernels instead of the materialised path
+    def _check_long_attn(self) -> None:
+        """The refusals of vitx_set_long_attn, from the configuration alone."""
+        c = self._cfg
+        if c.compute != N.COMPUTE_BF16:
+            raise ValueError(f"long_attn needs compute='bf16' (the streamed attention kernels are bf16 only), not {self.compute!r}")
+        if c.variant != N.VARIANT_VIT:
+            raise ValueError("long_attn: ViT models only (DeepViT, CaiT and the PatchMerger ViT keep their own attention paths)")
+        if c.dim_head != 64:
+            raise ValueError(f"long_attn needs dim_head=64, not {c.dim_head}")
+        if c.small_dataset:
+            raise ValueError("long_attn: not for vit_for_small_dataset models (LSA attention)")
+
+    def set_long_attn(self, on: bool) -> None:
+        """Switch the streamed-key attention path of sequences past 288 tokens on or off, between steps (vitx_set_long_attn)."""
+        if on:
+            self._check_long_attn()
+        if self._handle is not None and (on or self._long_attn):
+            N.check(N.lib().vitx_set_long_attn(self._handle, 1 if on else 0))
+        self._long_attn = bool(on)
+
+    def profile(self, fn):
+        """Runs fn() between vitx_profile_begin / _end: {class: (launches, total_ms)} (as the composite models' profile)."""
+        h, gen = self._ensure_handle(1), self._handle_gen
+        N.check(N.lib().vitx_profile_begin(h))
+        try:
+            fn()
+        finally:
+            if self._handle_gen != gen:   # fn() ran a batch above max_batch: that handle is gone and the new one was never profiled
+                raise N.VitxError(N.ERR_STATE, "profile: the device plan was rebuilt for a larger batch inside fn(); build the model at that batch first")
+            stats, n = (N.KernelStat * 256)(), C.c_int32()
+            N.check(N.lib().vitx_profile_end(h, stats, 256, C.byref(n)))
+        return {stats[i].name.decode(): (int(stats[i].launches), float(stats[i].total_ms)) for i in range(min(n.value, 256))}
+
     # ---- handle management
     def _ensure_handle(self, batch: int):
         l = N.lib()
@@ -213,6 +251,8 @@ class VitxModel(ParamBlob):
         N.check(l.vitx_create(C.byref(self._cfg), C.byref(h)))
         self._handle = h
         self._handle_gen += 1
+        if self._long_attn:
+            N.check(l.vitx_set_long_attn(h, 1))
         self._push_params()
         if opt is not None:
             mom, var, step = opt
