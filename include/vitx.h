@@ -305,8 +305,16 @@ int32_t vitx_debug_switches(char* out, int64_t cap, int64_t* needed);
 int32_t vitx_profile_begin(vitx_handle h);
 int32_t vitx_profile_end(vitx_handle h, vitx_kernel_stat* out, int32_t cap, int32_t* n_out);
 int32_t vitx_workspace_bytes(vitx_handle h, int64_t* bytes);
-/* copy a saved activation of the last forward to the host as fp32 (bisecting parity failures);
- * `which` in {"embed","x_in","y1","qkv","attn_out","x_mid","y2","hpre","act","x_out","pooled"} */
+/* copy a saved activation of the last forward to the host as fp32 (bisecting parity failures, per-stage parity tests);
+ * `which` in {"embed","x_in","y1","qkv","attn_out","x_mid","y2","hpre","act","x_out","pooled"}; after vitx_transformer_forward the
+ * block names describe that call's [b, n] rows.  In the bf16 mode "hpre" holds gelu'(h), what the backward multiplies by.
+ * LayerNorm statistics "mean1","rstd1","mean2","rstd2" [rows] and the softmax log-sum-exp "lse" [b, heads, n] (fused and streamed-key
+ * attention only) are fp32.
+ * Between a backward and the next forward, for the block whose backward ran last (`layer` must name it; layer 0 after a whole backward):
+ *   "d_hpre" [rows, mlp_dim], "d_attn_out" [rows, inner] (blocks with a to_out Dense), "d_qkv" packed [rows, 3 inner],
+ *   "d_y1" [rows, dim] -- the buffer both input-gradient GEMMs of a block write: after a whole block backward it holds d(y1), not d(y2).
+ * A variant or form that keeps one of these in another layout (CaiT [dq | dkv], reduced keys, the class-row last block) answers
+ * "activation not available for this variant". */
 int32_t vitx_debug_read(vitx_handle h, const char* which, int32_t layer, float* out_host,
                         int64_t cap_elems, int64_t* n_elems);
 /* raw GEMM micro-benchmark on the handle's stream: C[M,N] = A[M,K] * B[N,K]^T (bf16 operands,

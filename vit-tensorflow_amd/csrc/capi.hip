@@ -819,13 +819,16 @@ int32_t vitx_debug_read(vitx_handle h, const char* which, int32_t layer, float* 
   CAPI_TRY
   if (!h || !which) return fail(VITX_ERR_INVALID, "null argument");
   const vitx_config& c = h->cfg;
-  const int b = h->last_b;
+  // the saved state of a transformer_forward(tokens) has its own geometry (engine_transformer_forward records tf_b / tf_n, not last_*)
+  const bool tf = h->have_tf && !h->have_fwd;
+  const int b = tf ? h->tf_b : h->last_b, ntok = tf ? h->tf_n : h->last_ntok;
   // layer indexes the concatenation of all stages (CaiT: patch blocks then cls blocks)
   Stage* st = nullptr;
-  int l = layer, nq = h->last_ntok, nk = h->last_ntok;
+  int l = layer, nq = ntok, nk = ntok, si = 0;
   for (auto& s : h->stages) {
     if (l < s.depth) { st = &s; break; }
     l -= s.depth;
+    ++si;
   }
   const std::string w(which);
   const void* src = nullptr;
@@ -864,6 +867,24 @@ int32_t vitx_debug_read(vitx_handle h, const char* which, int32_t layer, float* 
     else if (w == "attn_out") { src = ba.o; cols = ld = h->inner; is_t = true; }
     else if (w == "hpre") { src = ba.hpre; cols = ld = c.mlp_dim; is_t = true; }
     else if (w == "act") { src = ba.act; cols = ld = c.mlp_dim; is_t = true; }
+    else if (w == "mean1") { src = ba.mean1; cols = ld = 1; }
+    else if (w == "rstd1") { src = ba.rstd1; cols = ld = 1; }
+    else if (w == "mean2") { src = ba.mean2; cols = ld = 1; }
+    else if (w == "rstd2") { src = ba.rstd2; cols = ld = 1; }
+    else if (w == "lse") {   // [b, heads, n] as the fused and streamed attention kernels save it; the other attention forms keep another record (or none)
+      if (ba.lse_bhn) { src = ba.lse; rows = (int64_t)b * c.heads; cols = ld = nq; }
+    }
+    else if (w == "d_hpre" || w == "d_attn_out" || w == "d_qkv" || w == "d_y1") {
+      // intermediates of the backward: handle-level buffers that hold the block whose backward ran last, and only in the layouts recorded there
+      const auto& br = h->bwd_read;
+      if (br.si == si && br.l == l && br.rows == rows) {
+        if (w == "d_hpre" && br.dh) { src = h->d_h; cols = ld = c.mlp_dim; }
+        else if (w == "d_attn_out" && br.dout) { src = h->d_o; cols = ld = h->inner; }
+        else if (w == "d_qkv" && br.dqkv) { src = h->d_qkv; cols = ld = 3 * h->inner; }
+        else if (w == "d_y1" && br.dy1) { src = h->d_y; cols = ld = c.dim; }
+      }
+      is_t = true;
+    }
     else return fail(VITX_ERR_INVALID, "unknown activation name");
   }
   if (!src) return fail(VITX_ERR_INVALID, "activation not available for this variant");

@@ -94,6 +94,7 @@ struct BlockActs {
   int sc_pi = 0;                    // index of the tensor that multiplies V
   bool sc_no_mixed = false;         // kept by the one-kernel DeepViT forward: sc_keep[1] (the mixed scores) was not written
   bool sc_a2_bf16 = false;   // sc_keep[2] holds bf16 [nq][round_up(nk, 8)] planes (one-kernel forward with the one-kernel backward as its reader)
+  bool lse_bhn = false;             // the last forward of this block ran the fused or the streamed-key attention on every row: lse holds [b, heads, n] (vitx_debug_read)
   bool attn_streamed = false;       // the last forward of this block ran the streamed-key attention (attn_stream.hip): its backward does too
   int par_first = 0, par_last = 0;   // backward order inside a group of parallel half-blocks: first / last one processed (1 + 1 = alone)
 };
@@ -198,6 +199,10 @@ struct vitx_engine {
   float* g2 = nullptr;               // parallel branches: the layer-input gradient being accumulated while g still feeds the other branches
   float* g = nullptr; void* g_lp = nullptr; float* g_ctx = nullptr;  // residual gradient stream (+T copy), CaiT patch-output grad
   void *d_h = nullptr, *d_y = nullptr, *d_o = nullptr, *d_qkv = nullptr, *d_ctx = nullptr, *d_br = nullptr;
+  // test hook (vitx_debug_read of the backward's intermediates): the block whose backward ran last and which of the buffers above it left in
+  // the plain layout -- d_h [rows, mlp_dim], d_o [rows, inner] (a to_out Dense exists), d_qkv packed [rows, 3 inner], d_y = d(y1) [rows, dim].
+  // Any block forward clears it (si = -1): the names are valid between a backward and the next forward only.
+  struct BwdRead { int si = -1, l = -1, rows = 0; bool dh = false, dout = false, dqkv = false, dy1 = false; } bwd_read;
   bf16_t *xt = nullptr, *dyt = nullptr; int64_t t_rows = 0;
   float* partial_ws = nullptr; int64_t partial_elems = 0;
   float* red_ws = nullptr; int64_t red_elems = 0;

@@ -1153,6 +1153,7 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
   const int rows = b * nq;
   const int nk = reduced_keys(c) ? global_keys(c) : nq + nc;   // (global_k / conv_proj handles: the keys are the reduced map)
   const double lnb = (double)rows * d * (4 + esz);
+  e->bwd_read.si = -1;   // the backward's intermediates no longer belong to the saved activations
   if (!ba.skip_attn) {
   {
     Prof pr(e, "layernorm_fwd", 0, lnb);
@@ -1224,6 +1225,7 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
     return VITX_ERR_UNSUPPORTED;
   }
   ba.attn_streamed = false;
+  ba.lse_bhn = false;
   if (c.small_dataset) {   // LSA (vit_for_small_dataset.py:109-117): learned temperature, masked diagonal
     Prof pr(e, "attn_lsa_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
     launch_attn_lsa_fwd(ba.qkv, ba.o, ba.lse, T, b, nq, c.heads, c.dim_head, e->params + bp.temp, e->stream);
@@ -1240,12 +1242,14 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
     // (class-row form: one live query row per image -- q / o traffic and the products of one row, k and v of every row)
     const double live = cls_rows ? 1.0 / nq : 1.0;
     Prof pr(e, "attn_bf16_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head * live, (double)rows * inner * (2 + 2 * live) * esz);
+    ba.lse_bhn = !cls_rows;
     launch_attn_bf16_fwd((const bf16_t*)ba.qkv, (bf16_t*)ba.o, ba.lse, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), (const bf16_t*)e->zero_page, (e->reverse_mask >> 2) & 1, e->stream,
                          cls_rows ? 1 : 0);
   } else if (use_stream_attn(e, nq)) {
     if (!attn_stream_fits(b, nq, c.heads)) { err = "long_attn: the streamed attention kernels take b * heads <= 65535 and n * 3 * heads * 64 < 2^30 elements per image"; return VITX_ERR_UNSUPPORTED; }
     Prof pr(e, "attn_stream_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
     ba.attn_streamed = true;
+    ba.lse_bhn = true;
     launch_attn_stream_fwd((const bf16_t*)ba.qkv, (bf16_t*)ba.o, ba.lse, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), e->stream);
   } else if (use_fewkey_attn(e, b, nq, nk)) {   // twins_svt.py:184-187
     Prof pr(e, "attn_fewkey_fwd", 4.0 * b * c.heads * (double)nq * nk * c.dim_head, ((double)rows * inner * 2 + (double)b * nk * 2 * inner) * esz);
@@ -1523,6 +1527,7 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
                         e->grads + bp.ln2_g, e->grads + bp.ln2_b, fc2_bias_in_ln ? e->grads + bp.fc2.b : nullptr, rows, fuse ? &nb : nullptr);
   }
   }   // !skip_mlp
+  e->bwd_read = vitx_engine::BwdRead{si, l, rows, !cls_rows && !ba.skip_mlp, false, false, false};
   if (ba.skip_attn) {
     report_ready(e, bp.p_begin, bp.p_end - bp.p_begin);
     return VITX_OK;
@@ -1752,6 +1757,10 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
     block_layernorm_bwd(e, e->d_y, T, d, ba.ln1_src ? ba.ln1_src : ba.x_in, ba.mean1, ba.rstd1, e->params + bp.ln1_g, ln_gin, ln_gout, ln_glp,
                         e->grads + bp.ln1_g, e->grads + bp.ln1_b, out_bias_in_ln ? e->grads + bp.out.b : nullptr, rows, fuse ? &nb : nullptr);
   }
+  // (vitx_debug_read) only the packed form of the last branch above leaves d(q | k | v) as [rows, 3 inner]; the class-row form and the [dq | dkv] forms are not read
+  const bool plain = !cls_rows && c.variant != VITX_VARIANT_CAIT && !c.conv_proj_kernel && !c.global_k;
+  e->bwd_read.dout = plain && bp.has_out;
+  e->bwd_read.dqkv = e->bwd_read.dy1 = plain;
   report_ready(e, bp.p_begin, bp.p_end - bp.p_begin);
   return VITX_OK;
 }

@@ -30,7 +30,7 @@ __device__ __forceinline__ void wp_store16(bf16_t* base, uint32_t elem_off, bf16
 // patterns) they are read from a 15-KiB LDS table; smaller |x| take the first entry of their sign (Phi = 1/2, gelu' = 1/2 to bf16 precision), larger
 // ones the last (Phi = 1 or 0, gelu' = 1 or 0).  Entry = Phi(x) as fp16 (high half) | gelu'(x) as bf16 (low half); gelu(x) = x * Phi(x), so both
 // ends are exact without a fix-up.  Built on the host from erf in double precision (closer to the exact-erf GELU of vit.py:34 than the degree-7
-// polynomial of the other epilogues: |Phi error| <= 2.4e-4 relative, below a quarter of a bf16 ulp).  Why: the polynomial form costs 17.5 VALU issue
+// polynomial of the other epilogues: the fp16 store leaves |Phi error| <= 2.4e-4 absolute, 4.9e-4 relative, an eighth of a bf16 ulp of Phi).  Why: the polynomial form costs 17.5 VALU issue
 // slots per element (two v_exp_f32 per pair at quarter rate), the epilogue of a 256 x 256 tile 18k cycles per SIMD next to a 33k-cycle K loop; the
 // table form ~11 slots and one LDS gather per element (the LDS is idle in the epilogue).
 constexpr int GT_LO = (127 - 12) << 7, GT_NE = ((127 + 3) << 7) - GT_LO, GT_BYTES = 2 * GT_NE * 4;   // 14720, 1920 entries per sign, 15360 B
