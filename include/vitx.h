@@ -755,6 +755,73 @@ int32_t vitx_crossformer_window_attn(vitx_crossformer_handle m, const float* qkv
 int32_t vitx_crossformer_partition(vitx_crossformer_handle m, const float* in_host, float* out_host, int32_t b, int32_t H, int32_t W, int32_t g,
                                    int32_t c, int32_t inverse);
 
+/* ---- RegionViT (regionvit.py:184-263): a local map (Conv2D 8x8 stride 4 'SAME', or three 3x3 convolutions with LayerNormalization and GELU
+ * between them, :210-221) and a region map (the (c p1 p2) patches of local_patch_size * window_size pixels through a 1x1 convolution, :223-226);
+ * per stage a Downsample (3x3 stride 2 'SAME', stages 2-4) applied to BOTH maps with the same kernel, an optional PEG on the local map, and an
+ * R2LTransformer (:118-182): per layer the region tokens attend to each other, every window of the local map gets its region token prepended,
+ * the windows run attention -- THE SAME Attention weights, plus the stage's learned relative position bias (an Embedding [(2 ws - 1)^2, 4],
+ * shared by the stage's layers, zero for the region token) -- and the MLP, and the two are split again.  Attention is pre-norm with 4 heads of
+ * 32 (:80).  Then mean over the region map, LayerNormalization, Dense (:243-247).  A stage drives two vitx_config.nest_block engines: one over
+ * the (b * windows) sequences of 1 + window tokens with the per-head bias (small-head BIAS kernels or, bf16 with at most 64 tokens, the window
+ * kernels), one over the b region sequences whose blocks stop behind the attention; both hold the layer's attention weights and the gradients
+ * are summed.  The embedding's gradient is the sum over sequences and layers of dS, gathered back through the index.  A handle of its own;
+ * parameter order in DESIGN.md section 26.  Only the deterministic path (ff_dropout 0) exists; attn_dropout is unused by the reference. */
+typedef struct vitx_regionvit_config {
+  /* the image the handle is built for; both 0 is allowed for the host-only table calls (no parameter depends on the image size) */
+  int32_t image_h, image_w;
+  int32_t num_classes;              /* regionvit.py:189 */
+  int32_t dim[4], depth[4];         /* :186-187 */
+  int32_t window_size;              /* :188 */
+  int32_t local_patch_size;         /* :191 */
+  int32_t tokenize_local_3_conv;    /* :190 */
+  int32_t use_peg;                  /* :192 */
+  float ln_eps;                     /* <= 0: Keras LayerNormalization's 1e-3 */
+  int32_t compute;                  /* VITX_COMPUTE_*: the transformer blocks' mode; encoders, Downsample, PEG and head keep fp32 */
+  int32_t max_batch;
+  int32_t device_id;
+  /* the window attention kernels (attn_window.hip) for the window sequences of at most 64 tokens in the bf16 mode.  0: the measured default
+   * (DESIGN.md section 26).  1: wherever they apply.  -1: nowhere.  More tokens, and the fp32 / bf16x3 modes, take the small-head kernels. */
+  int32_t window_attn;
+  int32_t reserved[7];
+} vitx_regionvit_config;
+typedef struct vitx_regionvit* vitx_regionvit_handle;
+/* host only, no GPU needed */
+int32_t vitx_regionvit_param_table_size(const vitx_regionvit_config* cfg, int64_t* n_tensors, int64_t* n_elems);
+int32_t vitx_regionvit_param_table_entry(const vitx_regionvit_config* cfg, int64_t index, char* name, int32_t name_cap, int64_t shape[4],
+                                         int32_t* rank, int64_t* offset_elems);
+int32_t vitx_regionvit_create(const vitx_regionvit_config* cfg, vitx_regionvit_handle* out);
+int32_t vitx_regionvit_destroy(vitx_regionvit_handle m);
+/* set_params / params_changed also gather every stage's position bias from its embedding table again */
+int32_t vitx_regionvit_set_params(vitx_regionvit_handle m, const float* host_blob, int64_t n_elems);
+int32_t vitx_regionvit_get_params(vitx_regionvit_handle m, float* host_blob, int64_t n_elems);
+int32_t vitx_regionvit_get_grads(vitx_regionvit_handle m, float* host_blob, int64_t n_elems);
+int32_t vitx_regionvit_params_dev(vitx_regionvit_handle m, float** dev_ptr, int64_t* n_elems);
+int32_t vitx_regionvit_grads_dev(vitx_regionvit_handle m, float** dev_ptr, int64_t* n_elems);
+int32_t vitx_regionvit_params_changed(vitx_regionvit_handle m);
+/* RegionViT.call (regionvit.py:249-263).  img [b, image_h, image_w, 3] NHWC; logits [b, num_classes] */
+int32_t vitx_regionvit_forward(vitx_regionvit_handle m, const float* img_host, int32_t b, float* logits_host);
+int32_t vitx_regionvit_forward_dev(vitx_regionvit_handle m, const float* img_dev, int32_t b, float* logits_dev_or_null);
+/* VJP of the last forward for d(logits): overwrites the gradient arena; d(img) only when asked for */
+int32_t vitx_regionvit_backward(vitx_regionvit_handle m, const float* dlogits_host, float* dimg_host_or_null);
+int32_t vitx_regionvit_backward_dev(vitx_regionvit_handle m, const float* dlogits_dev, float* dimg_dev_or_null);
+/* per-kernel-class timing as vitx_profile_begin / _end: every engine's block classes (attn_window_* / attn_small_*, attn_dbias among them) plus
+ * the composite's own (rv_im2col, rv_conv_gemm, rv_col2im, rv_windows, rv_peg, rv_encoder, rv_bias, rv_head) */
+int32_t vitx_regionvit_profile_begin(vitx_regionvit_handle m);
+int32_t vitx_regionvit_profile_end(vitx_regionvit_handle m, vitx_kernel_stat* out, int32_t cap, int32_t* n_out);
+/* "local.<s>" [b, lh_s, lw_s, dim_s] and "region.<s>" [b, rh_s, rw_s, dim_s]: the maps behind stage s; "bias.<s>" [4, n, n]: the stage's
+ * position bias as the attention adds it (n = 1 + window tokens; a stage without layers has none); "pooled" [b, dim_4] */
+int32_t vitx_regionvit_read(vitx_regionvit_handle m, const char* which, float* out_host, int64_t cap_elems, int64_t* n_elems);
+/* One biased attention alone with a per-head bias, on host tensors, for tests and bisecting (bf16 storage, heads of 32): qkv [b, n, 3, h, 32],
+ * d_o [b, n, h * 32], bias [h, n, n]; window_kernel != 0: attn_window.hip (1 <= n <= 64), 0: the BIAS form of the small-head kernels
+ * (n <= 288).  Tail rows as vitx_crossformer_window_attn.  dbias_host [h, n, n]: the sum over the b sequences of dS. */
+int32_t vitx_regionvit_attn(vitx_regionvit_handle m, const float* qkv_host, const float* d_o_host, const float* bias_host, int32_t b, int32_t n, int32_t h,
+                            int32_t tail_rows, float tail_value, int32_t window_kernel, float* o_host, float* lse_host, float* dqkv_host,
+                            float* dbias_host);
+/* the window partition kernels on host tensors: inverse == 0 joins region [b, rh, rw, c] and local [b, rh * wh, rw * ww, c] into
+ * tokens [(b rh rw), 1 + wh * ww, c]; inverse != 0 splits tokens back into the two */
+int32_t vitx_regionvit_partition(vitx_regionvit_handle m, float* region_host, float* local_host, float* tokens_host, int32_t b, int32_t rh, int32_t rw,
+                                 int32_t wh, int32_t ww, int32_t c, int32_t inverse);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@
 // atomics, two runs give the same bits.
 #include "kernels.h"
 
+#include <algorithm>
 #include <cfloat>
 
 namespace {
@@ -72,11 +73,12 @@ __device__ __forceinline__ void lsa_row_times_staged(const float* wrow, int npad
 
 template <typename T, int DH, int R, bool PLAIN, bool BIAS = false>
 __global__ __launch_bounds__(256) void attn_lsa_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ o, float* __restrict__ lse,
-                                                           const float* __restrict__ temperature, float scale, int n, int h) {
+                                                           const float* __restrict__ temperature, float scale, int n, int h, int64_t bias_hs) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int L = lsa_pitch<T, DH>();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int bi = blockIdx.z, hi = blockIdx.y, q0 = blockIdx.x * LSA_TILE;
+  if (BIAS) temperature += (int64_t)hi * bias_hs;   // (BIAS: the head's [n, n] plane; stride 0 = one plane for every head)
   const int inner = h * DH, npad = lsa_npad(n);
   const int64_t ld = 3 * (int64_t)inner;
   T* Ks = (T*)smem;
@@ -167,11 +169,12 @@ __global__ __launch_bounds__(256) void attn_lsa_fwd_kernel(const T* __restrict__
 // A operand of P v.
 template <int DH, bool PLAIN, bool BIAS = false>
 __global__ __launch_bounds__(256) void attn_lsa_fwd_mfma_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o, float* __restrict__ lse,
-                                                                const float* __restrict__ temperature, float scale, int n, int h) {
+                                                                const float* __restrict__ temperature, float scale, int n, int h, int64_t bias_hs) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int DHP = DH < 32 ? 32 : DH, KP = DHP + 8, KS = DHP / 32, NT = (LSA_N_MAX + 15) / 16;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, lg = lane >> 4;
   const int bi = blockIdx.z, hi = blockIdx.y, r0 = blockIdx.x * LSA_TILE + wave * 16;
+  if (BIAS) temperature += (int64_t)hi * bias_hs;
   const int inner = h * DH, n16 = (n + 15) & ~15, n32 = (n + 31) & ~31, PP = n32 + 8;
   const int64_t ld = 3 * (int64_t)inner;
   bf16_t* Ks = (bf16_t*)smem;                 // [n16][KP]
@@ -261,11 +264,11 @@ template <int DH> size_t lsa_fwd_mfma_lds(int n) {
   return ((size_t)n16 * (DHP + 8) + (size_t)DH * PP + (size_t)LSA_WAVES * 16 * PP) * 2;
 }
 template <int DH, bool PLAIN, bool BIAS = false>
-void lsa_fwd_mfma_launch(const bf16_t* qkv, bf16_t* o, float* lse, int b, int n, int h, const float* t, float scale, hipStream_t s) {
+void lsa_fwd_mfma_launch(const bf16_t* qkv, bf16_t* o, float* lse, int b, int n, int h, const float* t, float scale, hipStream_t s, int64_t bhs = 0) {
   auto kern = attn_lsa_fwd_mfma_kernel<DH, PLAIN, BIAS>;
   vitx_set_max_smem((const void*)kern, LSA_LDS_MAX);
   const size_t lds = lsa_fwd_mfma_lds<DH>(n);
-  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, lse, t, scale, n, h);
+  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, lse, t, scale, n, h, bhs);
 }
 
 // KEYS = false: the tile's rows are queries, K and V are staged: d(q), the row sums D = dO . o (kept in dsum for the other pass) and this workgroup's
@@ -275,12 +278,13 @@ template <typename T, int DH, int R, bool KEYS, bool PLAIN, bool BIAS = false>
 __global__ __launch_bounds__(256) void attn_lsa_bwd_kernel(const T* __restrict__ qkv, const T* __restrict__ o, const T* __restrict__ d_o,
                                                            const float* __restrict__ lse, float* __restrict__ dsum, T* __restrict__ dqkv,
                                                            const float* __restrict__ temperature, float scale, float* __restrict__ dt_part, int n,
-                                                           int h) {
+                                                           int h, int64_t bias_hs) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ float dt_wave[LSA_WAVES];
   constexpr int L = lsa_pitch<T, DH>();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int bi = blockIdx.z, hi = blockIdx.y, t0 = blockIdx.x * LSA_TILE;
+  if (BIAS) temperature += (int64_t)hi * bias_hs;
   const int inner = h * DH, npad = lsa_npad(n);
   const int64_t ld = 3 * (int64_t)inner;
   T* As = (T*)smem;          // dotted with the row's first vector: the scores
@@ -416,12 +420,13 @@ __global__ __launch_bounds__(256) void attn_lsa_bwd_mfma_kernel(const bf16_t* __
                                                                 const bf16_t* __restrict__ d_o, const float* __restrict__ lse,
                                                                 float* __restrict__ dsum, bf16_t* __restrict__ dqkv,
                                                                 const float* __restrict__ temperature, float scale, float* __restrict__ dt_part,
-                                                                int n, int h) {
+                                                                int n, int h, int64_t bias_hs) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ float dt_wave[LSA_WAVES];
   constexpr int DHP = DH < 32 ? 32 : DH, KP = DHP + 8, KS = DHP / 32, TP = LSA_NC + 8, NTC = LSA_NC / 16, ND = DH / 16;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, lg = lane >> 4;
   const int bi = blockIdx.z, hi = blockIdx.y, r0 = blockIdx.x * LSA_TILE + wave * 16;
+  if (BIAS) temperature += (int64_t)hi * bias_hs;
   const int inner = h * DH;
   const int64_t ld = 3 * (int64_t)inner;
   bf16_t* X0s = (bf16_t*)smem;              // [NC][KP] rows dotted with the first fragment: the scores
@@ -543,18 +548,18 @@ __global__ __launch_bounds__(256) void attn_lsa_bwd_mfma_kernel(const bf16_t* __
 }
 template <int DH, bool KEYS, bool PLAIN, bool BIAS = false>
 void lsa_bwd_mfma_launch(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o, const float* lse, float* dsum, bf16_t* dqkv, int b, int n, int h,
-                         const float* t, float scale, float* part, hipStream_t s) {
+                         const float* t, float scale, float* part, hipStream_t s, int64_t bhs = 0) {
   constexpr int DHP = DH < 32 ? 32 : DH, KP = DHP + 8, TP = LSA_NC + 8;
   const size_t lds = ((size_t)2 * LSA_NC * KP + (size_t)(KEYS ? 2 : 1) * DH * TP + (size_t)LSA_WAVES * (KEYS ? 2 : 1) * 16 * TP) * 2;
   auto kern = attn_lsa_bwd_mfma_kernel<DH, KEYS, PLAIN, BIAS>;
   vitx_set_max_smem((const void*)kern, LSA_LDS_MAX);
-  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, d_o, lse, dsum, dqkv, t, scale, part, n, h);
+  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, d_o, lse, dsum, dqkv, t, scale, part, n, h, bhs);
 }
 template <int DH, bool PLAIN, bool BIAS = false>
 void lsa_bwd_mfma_dh(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o, const float* lse, float* dsum, bf16_t* dqkv, int b, int n, int h,
-                     const float* t, float scale, float* part, hipStream_t s) {
-  lsa_bwd_mfma_launch<DH, false, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);   // (first: it writes the row sums the key pass reads)
-  lsa_bwd_mfma_launch<DH, true, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
+                     const float* t, float scale, float* part, hipStream_t s, int64_t bhs = 0) {
+  lsa_bwd_mfma_launch<DH, false, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s, bhs);   // (first: it writes the row sums the key pass reads)
+  lsa_bwd_mfma_launch<DH, true, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s, bhs);
 }
 
 // second pass of the temperature gradient: one workgroup, every thread a fixed strided share, then a fixed tree
@@ -579,16 +584,16 @@ template <typename T, int DH> size_t lsa_bwd_lds(int n, int R, bool keys) {
 }
 
 template <typename T, int DH, int R, bool PLAIN, bool BIAS = false>
-void lsa_fwd_launch(const T* qkv, T* o, float* lse, int b, int n, int h, const float* t, float scale, size_t lds, hipStream_t s) {
+void lsa_fwd_launch(const T* qkv, T* o, float* lse, int b, int n, int h, const float* t, float scale, size_t lds, hipStream_t s, int64_t bhs = 0) {
   auto kern = attn_lsa_fwd_kernel<T, DH, R, PLAIN, BIAS>;
   vitx_set_max_smem((const void*)kern, LSA_LDS_MAX);
-  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, lse, t, scale, n, h);
+  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, lse, t, scale, n, h, bhs);
 }
 template <typename T, int DH, bool PLAIN, bool BIAS = false>
-void lsa_fwd_dh(const T* qkv, T* o, float* lse, int b, int n, int h, const float* t, float scale, hipStream_t s) {
-  if (lsa_fwd_lds<T, DH>(n, 4) <= (size_t)LSA_LDS_MAX) lsa_fwd_launch<T, DH, 4, PLAIN, BIAS>(qkv, o, lse, b, n, h, t, scale, lsa_fwd_lds<T, DH>(n, 4), s);
-  else if (lsa_fwd_lds<T, DH>(n, 2) <= (size_t)LSA_LDS_MAX) lsa_fwd_launch<T, DH, 2, PLAIN, BIAS>(qkv, o, lse, b, n, h, t, scale, lsa_fwd_lds<T, DH>(n, 2), s);
-  else lsa_fwd_launch<T, DH, 1, PLAIN, BIAS>(qkv, o, lse, b, n, h, t, scale, lsa_fwd_lds<T, DH>(n, 1), s);
+void lsa_fwd_dh(const T* qkv, T* o, float* lse, int b, int n, int h, const float* t, float scale, hipStream_t s, int64_t bhs = 0) {
+  if (lsa_fwd_lds<T, DH>(n, 4) <= (size_t)LSA_LDS_MAX) lsa_fwd_launch<T, DH, 4, PLAIN, BIAS>(qkv, o, lse, b, n, h, t, scale, lsa_fwd_lds<T, DH>(n, 4), s, bhs);
+  else if (lsa_fwd_lds<T, DH>(n, 2) <= (size_t)LSA_LDS_MAX) lsa_fwd_launch<T, DH, 2, PLAIN, BIAS>(qkv, o, lse, b, n, h, t, scale, lsa_fwd_lds<T, DH>(n, 2), s, bhs);
+  else lsa_fwd_launch<T, DH, 1, PLAIN, BIAS>(qkv, o, lse, b, n, h, t, scale, lsa_fwd_lds<T, DH>(n, 1), s, bhs);
 }
 template <typename T>
 void lsa_fwd_t(const T* qkv, T* o, float* lse, int b, int n, int h, int dh, const float* t, hipStream_t s) {
@@ -599,25 +604,25 @@ void lsa_fwd_t(const T* qkv, T* o, float* lse, int b, int n, int h, int dh, cons
 
 template <typename T, int DH, int R, bool KEYS, bool PLAIN, bool BIAS = false>
 void lsa_bwd_launch(const T* qkv, const T* o, const T* d_o, const float* lse, float* dsum, T* dqkv, int b, int n, int h, const float* t, float scale,
-                    float* part, hipStream_t s) {
+                    float* part, hipStream_t s, int64_t bhs = 0) {
   auto kern = attn_lsa_bwd_kernel<T, DH, R, KEYS, PLAIN, BIAS>;
   vitx_set_max_smem((const void*)kern, LSA_LDS_MAX);
   const size_t lds = lsa_bwd_lds<T, DH>(n, R, KEYS);
-  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, d_o, lse, dsum, dqkv, t, scale, part, n, h);
+  hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(n, LSA_TILE), h, b), dim3(256), lds, s, qkv, o, d_o, lse, dsum, dqkv, t, scale, part, n, h, bhs);
 }
 // each pass with the most rows per wave whose LDS rows still fit beside the staged operands
 template <typename T, int DH, bool KEYS, bool PLAIN, bool BIAS = false>
 void lsa_bwd_pass(const T* qkv, const T* o, const T* d_o, const float* lse, float* dsum, T* dqkv, int b, int n, int h, const float* t, float scale,
-                  float* part, hipStream_t s) {
-  if (lsa_bwd_lds<T, DH>(n, 4, KEYS) <= (size_t)LSA_LDS_MAX) lsa_bwd_launch<T, DH, 4, KEYS, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
-  else if (lsa_bwd_lds<T, DH>(n, 2, KEYS) <= (size_t)LSA_LDS_MAX) lsa_bwd_launch<T, DH, 2, KEYS, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
-  else lsa_bwd_launch<T, DH, 1, KEYS, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
+                  float* part, hipStream_t s, int64_t bhs = 0) {
+  if (lsa_bwd_lds<T, DH>(n, 4, KEYS) <= (size_t)LSA_LDS_MAX) lsa_bwd_launch<T, DH, 4, KEYS, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s, bhs);
+  else if (lsa_bwd_lds<T, DH>(n, 2, KEYS) <= (size_t)LSA_LDS_MAX) lsa_bwd_launch<T, DH, 2, KEYS, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s, bhs);
+  else lsa_bwd_launch<T, DH, 1, KEYS, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s, bhs);
 }
 template <typename T, int DH, bool PLAIN, bool BIAS = false>
 void lsa_bwd_dh(const T* qkv, const T* o, const T* d_o, const float* lse, float* dsum, T* dqkv, int b, int n, int h, const float* t, float scale,
-                float* part, hipStream_t s) {
-  lsa_bwd_pass<T, DH, false, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);   // (first: it writes the row sums the key pass reads)
-  lsa_bwd_pass<T, DH, true, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s);
+                float* part, hipStream_t s, int64_t bhs = 0) {
+  lsa_bwd_pass<T, DH, false, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s, bhs);   // (first: it writes the row sums the key pass reads)
+  lsa_bwd_pass<T, DH, true, PLAIN, BIAS>(qkv, o, d_o, lse, dsum, dqkv, b, n, h, t, scale, part, s, bhs);
 }
 template <typename T>
 void lsa_bwd_t(const T* qkv, const T* o, const T* d_o, const float* lse, float* dsum, T* dqkv, int b, int n, int h, int dh, const float* t, float* part,
@@ -661,10 +666,10 @@ void launch_attn_lsa_bwd(const void* qkv, const void* o, const void* d_o, const 
 bool attn_small_supported(int n, int dim_head) { return (dim_head == 16 || dim_head == 32) && n >= 1 && n <= LSA_N_MAX; }
 
 void launch_attn_small_fwd(const void* qkv, void* o, float* lse, int is_bf16, int b, int n, int h, int dim_head, float scale, hipStream_t s,
-                           const float* bias) {
+                           const float* bias, int64_t bias_hs) {
   if (bias) {   // BIAS mode (crossformer.py:156-168): s = scale q k^T + bias[i][j]; dim_head 32 only; the bias travels in the temperature slot
-    if (is_bf16) lsa_fwd_mfma_launch<32, true, true>((const bf16_t*)qkv, (bf16_t*)o, lse, b, n, h, bias, scale, s);
-    else lsa_fwd_dh<float, 32, true, true>((const float*)qkv, (float*)o, lse, b, n, h, bias, scale, s);
+    if (is_bf16) lsa_fwd_mfma_launch<32, true, true>((const bf16_t*)qkv, (bf16_t*)o, lse, b, n, h, bias, scale, s, bias_hs);
+    else lsa_fwd_dh<float, 32, true, true>((const float*)qkv, (float*)o, lse, b, n, h, bias, scale, s, bias_hs);
     return;
   }
   if (is_bf16) {
@@ -675,10 +680,10 @@ void launch_attn_small_fwd(const void* qkv, void* o, float* lse, int is_bf16, in
 }
 
 void launch_attn_small_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, float* dsum_ws, void* dqkv, int is_bf16, int b, int n, int h,
-                           int dim_head, float scale, hipStream_t s, const float* bias) {
-  if (bias) {   // the bias is a constant of the step: it is needed only to recompute P
-    if (is_bf16) lsa_bwd_mfma_dh<32, true, true>((const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)d_o, lse, dsum_ws, (bf16_t*)dqkv, b, n, h, bias, scale, nullptr, s);
-    else lsa_bwd_dh<float, 32, true, true>((const float*)qkv, (const float*)o, (const float*)d_o, lse, dsum_ws, (float*)dqkv, b, n, h, bias, scale, nullptr, s);
+                           int dim_head, float scale, hipStream_t s, const float* bias, int64_t bias_hs) {
+  if (bias) {   // d(q, k, v) need the bias only to recompute P (its own gradient: launch_attn_dbias)
+    if (is_bf16) lsa_bwd_mfma_dh<32, true, true>((const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)d_o, lse, dsum_ws, (bf16_t*)dqkv, b, n, h, bias, scale, nullptr, s, bias_hs);
+    else lsa_bwd_dh<float, 32, true, true>((const float*)qkv, (const float*)o, (const float*)d_o, lse, dsum_ws, (float*)dqkv, b, n, h, bias, scale, nullptr, s, bias_hs);
     return;
   }
   if (is_bf16) {
@@ -689,4 +694,85 @@ void launch_attn_small_bwd(const void* qkv, const void* o, const void* d_o, cons
     lsa_bwd_dh<float, 32, true>((const float*)qkv, (const float*)o, (const float*)d_o, lse, dsum_ws, (float*)dqkv, b, n, h, nullptr, scale, nullptr, s);
   else
     lsa_bwd_dh<float, 16, true>((const float*)qkv, (const float*)o, (const float*)d_o, lse, dsum_ws, (float*)dqkv, b, n, h, nullptr, scale, nullptr, s);
+}
+
+// ---------------------------------------------------------------------------------------------- d(bias) of a learned bias (regionvit.py:107,126)
+// d(bias)[h, i, j] = sum over the sequences of dS[h, i, j], dS = P o (dP - rowsum(dO o O)) = P o (dO_i . (v_j - o_i)): unscaled, the bias is added
+// behind the scale.  A kernel of its own that recomputes P from lse, so that it serves both biased attention families and every storage type:
+// one thread per DB_EPT entries (i, j) of one head, a workgroup walks a fixed slice of the sequences and keeps its sums in registers; one partial
+// [h, n, n] per slice, added in slice order by the second pass INTO the accumulator (a bias shared by the layers of a stage collects them all).
+// No atomics: the same bits every run.  Operands come straight from global memory (rows of 32 elements, the q / dO / o row shared by the
+// threads of a row of entries); not tuned.
+namespace {
+constexpr int DB_EPT = 8, DB_SLICES = 64;
+
+template <typename T>
+__global__ __launch_bounds__(256) void attn_dbias_part_kernel(const T* __restrict__ qkv, const T* __restrict__ o, const T* __restrict__ d_o,
+                                                              const float* __restrict__ lse, const float* __restrict__ bias, int64_t bias_hs, float scale,
+                                                              int b, int n, int h, int per, float* __restrict__ part) {
+  const int hi = blockIdx.y, sl = blockIdx.z, nn = n * n, inner = h * 32;
+  const int e0 = blockIdx.x * (256 * DB_EPT) + threadIdx.x;
+  const int64_t ld = 3 * (int64_t)inner;
+  const float* bh = bias + (int64_t)hi * bias_hs;
+  float acc[DB_EPT];
+#pragma unroll
+  for (int t = 0; t < DB_EPT; ++t) acc[t] = 0.f;
+  const int b1 = min(b, (sl + 1) * per);
+  for (int bi = sl * per; bi < b1; ++bi) {
+    const T* base = qkv + (int64_t)bi * n * ld + hi * 32;
+    const T* dob = d_o + (int64_t)bi * n * inner + hi * 32;
+    const T* ob = o + (int64_t)bi * n * inner + hi * 32;
+    const float* lse_h = lse + ((int64_t)bi * h + hi) * n;
+#pragma unroll
+    for (int t = 0; t < DB_EPT; ++t) {
+      const int e = e0 + t * 256;
+      if (e >= nn) continue;
+      const int i = e / n, j = e - i * n;
+      const T* qr = base + (int64_t)i * ld;
+      const T* kr = base + inner + (int64_t)j * ld;
+      const T* vr = kr + inner;
+      const T* gr = dob + (int64_t)i * inner;
+      const T* orow = ob + (int64_t)i * inner;
+      float sc = 0.f, dp = 0.f;
+#pragma unroll
+      for (int d = 0; d < 32; d += 4) {
+        const float4 q4 = ld4<T>(qr + d), k4 = ld4<T>(kr + d), v4 = ld4<T>(vr + d), g4 = ld4<T>(gr + d), o4 = ld4<T>(orow + d);
+        sc = fmaf(q4.x, k4.x, sc); sc = fmaf(q4.y, k4.y, sc); sc = fmaf(q4.z, k4.z, sc); sc = fmaf(q4.w, k4.w, sc);
+        dp = fmaf(g4.x, v4.x - o4.x, dp); dp = fmaf(g4.y, v4.y - o4.y, dp); dp = fmaf(g4.z, v4.z - o4.z, dp); dp = fmaf(g4.w, v4.w - o4.w, dp);
+      }
+      acc[t] += expf(fmaf(sc, scale, bh[e]) - lse_h[i]) * dp;
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < DB_EPT; ++t) {
+    const int e = e0 + t * 256;
+    if (e < nn) part[((int64_t)sl * h + hi) * nn + e] = acc[t];
+  }
+}
+
+// acc[e] += part[0][e] + part[1][e] + ... in slice order
+__global__ __launch_bounds__(256) void attn_dbias_reduce_kernel(const float* __restrict__ part, int slices, int64_t total, float* __restrict__ acc) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  float a = part[e];
+  for (int sl = 1; sl < slices; ++sl) a += part[(int64_t)sl * total + e];
+  acc[e] += a;
+}
+}  // namespace
+
+int64_t attn_dbias_ws_elems(int b, int n, int h) { return (int64_t)std::min(std::max(b, 1), DB_SLICES) * h * n * n; }
+
+void launch_attn_dbias(const void* qkv, const void* o, const void* d_o, const float* lse, int is_bf16, int b, int n, int h, float scale, const float* bias,
+                       int64_t bias_hs, float* ws, float* dbias_acc, hipStream_t s) {
+  if (b <= 0) return;
+  const int per = (int)ceil_div(b, DB_SLICES), slices = (int)ceil_div(b, per);
+  const int64_t total = (int64_t)h * n * n;
+  const dim3 grid((unsigned)ceil_div(n * n, 256 * DB_EPT), h, slices);
+  if (is_bf16)
+    hipLaunchKernelGGL(attn_dbias_part_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)d_o, lse, bias, bias_hs, scale, b, n,
+                       h, per, ws);
+  else
+    hipLaunchKernelGGL(attn_dbias_part_kernel<float>, grid, dim3(256), 0, s, (const float*)qkv, (const float*)o, (const float*)d_o, lse, bias, bias_hs, scale, b, n, h,
+                       per, ws);
+  hipLaunchKernelGGL(attn_dbias_reduce_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, (const float*)ws, slices, total, dbias_acc);
 }

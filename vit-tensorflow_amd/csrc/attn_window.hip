@@ -78,7 +78,7 @@ __device__ __forceinline__ void aw_store(bf16_t* __restrict__ dst, int64_t ld, c
 
 template <int NTT>
 __global__ __launch_bounds__(256) void attn_window_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o, float* __restrict__ lse,
-                                                              const float* __restrict__ bias, float scale, int n, int h, int nprob) {
+                                                              const float* __restrict__ bias, float scale, int n, int h, int nprob, int64_t bias_hs) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int N32 = NTT * 16, PP = N32 + 8;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, lg = lane >> 4;
@@ -87,10 +87,15 @@ __global__ __launch_bounds__(256) void attn_window_fwd_kernel(const bf16_t* __re
   float* bs = (float*)smem;
   bf16_t* X = (bf16_t*)(smem + (((size_t)n * n * 4 + 15) & ~(size_t)15)) + wave * ((N32 + 32) * PP);
   bf16_t* Y = X + N32 * PP;
+  // a per-head bias (bias_hs != 0): the workgroup stays on head blockIdx.x % h and walks sequences, so that one [n, n] plane is all it stages
+  const bool per_head = bias_hs != 0;
+  const int hfix = per_head ? (int)(blockIdx.x % h) : 0;
+  bias += (int64_t)hfix * bias_hs;
   for (int e = threadIdx.x; e < n * n; e += blockDim.x) bs[e] = bias[e];
   __syncthreads();
-  for (int p = blockIdx.x * AW_WAVES + wave; p < nprob; p += gridDim.x * AW_WAVES) {   // (wave-uniform)
-    const int bi = p / h, hi = p - bi * h;
+  const int pstep = (per_head ? gridDim.x / h : gridDim.x) * AW_WAVES, pend = per_head ? nprob / h : nprob;
+  for (int p = (per_head ? blockIdx.x / h : blockIdx.x) * AW_WAVES + wave; p < pend; p += pstep) {   // (wave-uniform)
+    const int bi = per_head ? p : p / h, hi = per_head ? hfix : p - bi * h;
     const bf16_t* base = qkv + (int64_t)bi * n * ld + hi * 32;
     bf16x8 qf[NTT], kf[NTT], vf[NTT];
 #pragma unroll
@@ -149,7 +154,7 @@ __global__ __launch_bounds__(256) void attn_window_fwd_kernel(const bf16_t* __re
 template <int NTT>
 __global__ __launch_bounds__(256) void attn_window_bwd_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o, const bf16_t* __restrict__ d_o,
                                                               const float* __restrict__ lse, bf16_t* __restrict__ dqkv, const float* __restrict__ bias,
-                                                              float scale, int n, int h, int nprob) {
+                                                              float scale, int n, int h, int nprob, int64_t bias_hs) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int N32 = NTT * 16, PP = N32 + 8;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, lg = lane >> 4;
@@ -158,10 +163,15 @@ __global__ __launch_bounds__(256) void attn_window_bwd_kernel(const bf16_t* __re
   float* bs = (float*)smem;
   bf16_t* X = (bf16_t*)(smem + (((size_t)n * n * 4 + 15) & ~(size_t)15)) + wave * ((N32 + 32) * PP);
   bf16_t* Y = X + N32 * PP;
+  // a per-head bias (bias_hs != 0): the workgroup stays on head blockIdx.x % h and walks sequences, so that one [n, n] plane is all it stages
+  const bool per_head = bias_hs != 0;
+  const int hfix = per_head ? (int)(blockIdx.x % h) : 0;
+  bias += (int64_t)hfix * bias_hs;
   for (int e = threadIdx.x; e < n * n; e += blockDim.x) bs[e] = bias[e];
   __syncthreads();
-  for (int p = blockIdx.x * AW_WAVES + wave; p < nprob; p += gridDim.x * AW_WAVES) {   // (wave-uniform)
-    const int bi = p / h, hi = p - bi * h;
+  const int pstep = (per_head ? gridDim.x / h : gridDim.x) * AW_WAVES, pend = per_head ? nprob / h : nprob;
+  for (int p = (per_head ? blockIdx.x / h : blockIdx.x) * AW_WAVES + wave; p < pend; p += pstep) {   // (wave-uniform)
+    const int bi = per_head ? p : p / h, hi = per_head ? hfix : p - bi * h;
     const bf16_t* base = qkv + (int64_t)bi * n * ld + hi * 32;
     const bf16_t* dob = d_o + (int64_t)bi * n * inner + hi * 32;
     const bf16_t* ob = o + (int64_t)bi * n * inner + hi * 32;
@@ -253,35 +263,39 @@ __global__ __launch_bounds__(256) void attn_window_bwd_kernel(const bf16_t* __re
 template <int NTT> size_t aw_lds(int n) {
   return (((size_t)n * n * 4 + 15) & ~(size_t)15) + (size_t)AW_WAVES * (NTT * 16 + 32) * (NTT * 16 + 8) * 2;
 }
-unsigned aw_grid(int nprob) { return (unsigned)std::min<int64_t>(ceil_div(nprob, AW_WAVES), 2048); }
+// per_head: a multiple of h workgroups, each on one head
+unsigned aw_grid(int nprob, int h, bool per_head) {
+  if (per_head) return (unsigned)(h * std::min<int64_t>(ceil_div(nprob / h, AW_WAVES), std::max(1, 2048 / h)));
+  return (unsigned)std::min<int64_t>(ceil_div(nprob, AW_WAVES), 2048);
+}
 
 }  // namespace
 
 bool attn_window_supported(int n, int dim_head) { return dim_head == 32 && n >= 1 && n <= 64; }
 
-void launch_attn_window_fwd(const bf16_t* qkv, bf16_t* o, float* lse, const float* bias, int b, int n, int h, float scale, hipStream_t s) {
+void launch_attn_window_fwd(const bf16_t* qkv, bf16_t* o, float* lse, const float* bias, int b, int n, int h, float scale, hipStream_t s, int64_t bias_hs) {
   const int nprob = b * h;
   if (nprob <= 0) return;
   if (n <= 32) {
     auto kern = attn_window_fwd_kernel<2>;
-    hipLaunchKernelGGL(kern, dim3(aw_grid(nprob)), dim3(256), aw_lds<2>(n), s, qkv, o, lse, bias, scale, n, h, nprob);
+    hipLaunchKernelGGL(kern, dim3(aw_grid(nprob, h, bias_hs != 0)), dim3(256), aw_lds<2>(n), s, qkv, o, lse, bias, scale, n, h, nprob, bias_hs);
   } else {
     auto kern = attn_window_fwd_kernel<4>;
     vitx_set_max_smem((const void*)kern, (int)aw_lds<4>(64));
-    hipLaunchKernelGGL(kern, dim3(aw_grid(nprob)), dim3(256), aw_lds<4>(n), s, qkv, o, lse, bias, scale, n, h, nprob);
+    hipLaunchKernelGGL(kern, dim3(aw_grid(nprob, h, bias_hs != 0)), dim3(256), aw_lds<4>(n), s, qkv, o, lse, bias, scale, n, h, nprob, bias_hs);
   }
 }
 
 void launch_attn_window_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o, const float* lse, bf16_t* dqkv, const float* bias, int b, int n, int h,
-                            float scale, hipStream_t s) {
+                            float scale, hipStream_t s, int64_t bias_hs) {
   const int nprob = b * h;
   if (nprob <= 0) return;
   if (n <= 32) {
     auto kern = attn_window_bwd_kernel<2>;
-    hipLaunchKernelGGL(kern, dim3(aw_grid(nprob)), dim3(256), aw_lds<2>(n), s, qkv, o, d_o, lse, dqkv, bias, scale, n, h, nprob);
+    hipLaunchKernelGGL(kern, dim3(aw_grid(nprob, h, bias_hs != 0)), dim3(256), aw_lds<2>(n), s, qkv, o, d_o, lse, dqkv, bias, scale, n, h, nprob, bias_hs);
   } else {
     auto kern = attn_window_bwd_kernel<4>;
     vitx_set_max_smem((const void*)kern, (int)aw_lds<4>(64));
-    hipLaunchKernelGGL(kern, dim3(aw_grid(nprob)), dim3(256), aw_lds<4>(n), s, qkv, o, d_o, lse, dqkv, bias, scale, n, h, nprob);
+    hipLaunchKernelGGL(kern, dim3(aw_grid(nprob, h, bias_hs != 0)), dim3(256), aw_lds<4>(n), s, qkv, o, d_o, lse, dqkv, bias, scale, n, h, nprob, bias_hs);
   }
 }

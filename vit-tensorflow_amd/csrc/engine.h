@@ -216,6 +216,11 @@ struct vitx_engine {
   // crossformer.hip sets them after engine_create and owns the buffers.  Empty: no bias, every other handle.
   std::vector<const float*> attn_bias;
   int attn_bias_n = 0;
+  // a learned bias (regionvit.py:126,153-155): attn_bias_hs != 0 is the element stride between the heads' [n, n] planes (0: one plane for every
+  // head); attn_dbias, when set, is a fp32 [heads, n, n] buffer every block's backward ADDS its sum over the sequences of dS into (fixed order,
+  // through attn_dbias_ws: attn_dbias_ws_elems floats).  regionvit.hip owns both buffers and zeroes attn_dbias at the start of its backward.
+  int64_t attn_bias_hs = 0;
+  float *attn_dbias = nullptr, *attn_dbias_ws = nullptr;
   bool window_attn = false;   // biased handles, bf16 mode, n <= 64: the one-wave-per-window kernels (attn_window.hip); crossformer.hip sets it per handle
   void* zero_page = nullptr;         // 256 B of zeros (source of the padded rows in the attention DMA staging)
   float* tmp_f32 = nullptr;          // [mp, max(d, pd)] fp32 scratch (dropout / dimg paths)

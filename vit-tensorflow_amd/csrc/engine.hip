@@ -1231,10 +1231,10 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
     launch_attn_lsa_fwd(ba.qkv, ba.o, ba.lse, T, b, nq, c.heads, c.dim_head, e->params + bp.temp, e->stream);
   } else if (attn_bias && use_window_attn(e, nq)) {   // crossformer.py:156-171, tiny windows
     Prof pr(e, "attn_window_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
-    launch_attn_window_fwd((const bf16_t*)ba.qkv, (bf16_t*)ba.o, ba.lse, attn_bias, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), e->stream);
+    launch_attn_window_fwd((const bf16_t*)ba.qkv, (bf16_t*)ba.o, ba.lse, attn_bias, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), e->stream, e->attn_bias_hs);
   } else if (use_small_attn(e, nq)) {   // nest.py:101-105
     Prof pr(e, "attn_small_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
-    launch_attn_small_fwd(ba.qkv, ba.o, ba.lse, T, b, nq, c.heads, c.dim_head, 1.0f / std::sqrt((float)c.dim_head), e->stream, attn_bias);
+    launch_attn_small_fwd(ba.qkv, ba.o, ba.lse, T, b, nq, c.heads, c.dim_head, 1.0f / std::sqrt((float)c.dim_head), e->stream, attn_bias, e->attn_bias_hs);
   } else if (use_fused_attn_x3(e, nq)) {
     Prof pr(e, "attn_x3_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
     launch_attn_x3_fwd((const float*)ba.qkv, (float*)ba.o, ba.lse, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), e->stream);
@@ -1708,11 +1708,11 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
     } else if (!e->attn_bias.empty() && use_window_attn(e, nq)) {
       Prof pr(e, "attn_window_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
       launch_attn_window_bwd((const bf16_t*)ba.qkv, (const bf16_t*)ba.o, (const bf16_t*)d_o, ba.lse, (bf16_t*)e->d_qkv, e->attn_bias[(size_t)l], b, nq, c.heads,
-                             1.0f / std::sqrt((float)c.dim_head), e->stream);
+                             1.0f / std::sqrt((float)c.dim_head), e->stream, e->attn_bias_hs);
     } else if (use_small_attn(e, nq)) {
       Prof pr(e, "attn_small_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
       launch_attn_small_bwd(ba.qkv, ba.o, d_o, ba.lse, e->dsum, e->d_qkv, T, b, nq, c.heads, c.dim_head, 1.0f / std::sqrt((float)c.dim_head), e->stream,
-                            e->attn_bias.empty() ? nullptr : e->attn_bias[(size_t)l]);
+                            e->attn_bias.empty() ? nullptr : e->attn_bias[(size_t)l], e->attn_bias_hs);
     } else if (use_fused_attn_x3(e, nq)) {
       Prof pr(e, "attn_x3_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
       launch_attn_x3_bwd((const float*)ba.qkv, (const float*)ba.o, (const float*)d_o, ba.lse, (float*)e->d_qkv, b, nq, c.heads,
@@ -1731,6 +1731,11 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
       int rc = ensure_scores(e, 4, (int64_t)b * c.heads * nq * round_up(nk, 4), err);
       if (rc != VITX_OK) return rc;
       attn_generic_bwd(e, bp, av, ag, b, &ba);
+    }
+    if (e->attn_dbias && !e->attn_bias.empty()) {   // regionvit.py:107 -- the bias is a variable: d(bias) = sum over the sequences of dS
+      Prof pr(e, "attn_dbias", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 5 * esz);
+      launch_attn_dbias(ba.qkv, ba.o, d_o, ba.lse, T, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), e->attn_bias[(size_t)l], e->attn_bias_hs,
+                        e->attn_dbias_ws, e->attn_dbias, e->stream);
     }
     EpiParams ep; ep.out = e->d_y; ep.ldo = d;
     ep.nt_out = (e->nt_mask >> 4) & 1;

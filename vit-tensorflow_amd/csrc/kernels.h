@@ -121,16 +121,36 @@ void launch_attn_lsa_bwd(const void* qkv, const void* o, const void* d_o, const 
 // dim_head in {16, 32}, 1 <= n <= LSA_N_MAX
 bool attn_small_supported(int n, int dim_head);
 // bias: optional fp32 [n, n] added to the scaled scores (dim_head 32 only; crossformer.py:165)
+// bias_hs: element stride between the heads' planes of a per-head bias [h, n, n] (regionvit.py:154); 0: one [n, n] plane for every head
 void launch_attn_small_fwd(const void* qkv, void* o, float* lse, int is_bf16, int b, int n, int h, int dim_head, float scale, hipStream_t s,
-                           const float* bias = nullptr);
+                           const float* bias = nullptr, int64_t bias_hs = 0);
 void launch_attn_small_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, float* dsum_ws, void* dqkv, int is_bf16, int b, int n, int h,
-                           int dim_head, float scale, hipStream_t s, const float* bias = nullptr);
+                           int dim_head, float scale, hipStream_t s, const float* bias = nullptr, int64_t bias_hs = 0);
 // attn_window.hip -- biased attention of tiny windows (crossformer.py:149-172): bf16 storage, dim_head 32, 1 <= n <= 64; one wave per (sequence, head);
 // s = scale q k^T + bias[n, n] (fp32), softmax, P v on the packed qkv [b, n, 3, h, 32] and its VJP (d(q, k, v) written by the same wave: no workspace)
 bool attn_window_supported(int n, int dim_head);
-void launch_attn_window_fwd(const bf16_t* qkv, bf16_t* o, float* lse, const float* bias, int b, int n, int h, float scale, hipStream_t s);
+// bias_hs != 0: a per-head bias [h, n, n]; a workgroup then stays on one head (its LDS holds one plane, as with the shared bias)
+void launch_attn_window_fwd(const bf16_t* qkv, bf16_t* o, float* lse, const float* bias, int b, int n, int h, float scale, hipStream_t s, int64_t bias_hs = 0);
 void launch_attn_window_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o, const float* lse, bf16_t* dqkv, const float* bias, int b, int n, int h,
-                            float scale, hipStream_t s);
+                            float scale, hipStream_t s, int64_t bias_hs = 0);
+// d(bias) of a learned bias (attn_lsa.hip; both families, fp32 or bf16 storage, dim_head 32, n <= LSA_N_MAX): dbias_acc [h, n, n] += the sum over the
+// b sequences of dS = P o (dP - rowsum(dO o O)), P recomputed from lse; per-slice partials in ws (attn_dbias_ws_elems floats), summed in slice order
+int64_t attn_dbias_ws_elems(int b, int n, int h);
+void launch_attn_dbias(const void* qkv, const void* o, const void* d_o, const float* lse, int is_bf16, int b, int n, int h, float scale, const float* bias,
+                       int64_t bias_hs, float* ws, float* dbias_acc, hipStream_t s);
+// regionvit_ops.hip -- RegionViT (regionvit.py) outside its transformer blocks
+// tokens[(b wy wx), 0, c] = region[b, wy, wx, c]; tokens[(b wy wx), 1 + p1 ww + p2, c] = local[b, wy wh + p1, wx ww + p2, c] (:163-168) and the split
+// back (:175-177); each is the other's VJP
+void launch_rv_join(const float* region, const float* local, float* tokens, int b, int rh, int rw, int wh, int ww, int c, hipStream_t s);
+void launch_rv_split(const float* tokens, float* region, float* local, int b, int rh, int rw, int wh, int ww, int c, hipStream_t s);
+// bias[h, 1 + i, 1 + j] = table[(dh + ws - 1) + (dw + ws - 1)(2 ws - 1), h] for tokens i, j of a wh x ww window, row 0 and column 0 zero (:144-155);
+// dtable[idx, h] = the sum of dbias[h, 1 + i, 1 + j] over the pairs with that index, in (y, x) order; an index no pair has gets 0
+void launch_rv_bias_build(const float* table, float* bias, int ws, int wh, int ww, int heads, hipStream_t s);
+void launch_rv_table_grad(const float* dbias, float* dtable, int ws, int wh, int ww, int heads, hipStream_t s);
+void launch_rv_add(float* dst, const float* src, int64_t n, hipStream_t s);   // dst += src
+// exact GELU (:28) on fp32 and its VJP (dx = dy * gelu'(x))
+void launch_rv_gelu_fwd(const float* x, float* y, int64_t n, hipStream_t s);
+void launch_rv_gelu_bwd(const float* x, const float* dy, float* dx, int64_t n, hipStream_t s);
 // crossformer_ops.hip -- CrossFormer (crossformer.py) outside its transformer blocks
 // tokens[(b h w), (l1 l2), c] = x[b, l1 * (H / g) + h, l2 * (W / g) + w, c] ('b (l1 h) (l2 w) d -> (b h w) l1 l2 d', :146) and its inverse (:178);
 // each is the other's VJP

@@ -140,6 +140,16 @@ class CrossFormerConfig(C.Structure):
     ]
 
 
+class RegionViTConfig(C.Structure):
+    _fields_ = [
+        ("image_h", C.c_int32), ("image_w", C.c_int32), ("num_classes", C.c_int32),
+        ("dim", C.c_int32 * 4), ("depth", C.c_int32 * 4), ("window_size", C.c_int32), ("local_patch_size", C.c_int32),
+        ("tokenize_local_3_conv", C.c_int32), ("use_peg", C.c_int32),
+        ("ln_eps", C.c_float), ("compute", C.c_int32), ("max_batch", C.c_int32), ("device_id", C.c_int32),
+        ("window_attn", C.c_int32), ("reserved", C.c_int32 * 7),
+    ]
+
+
 class CrossViTConfig(C.Structure):
     _fields_ = [
         ("image_size", C.c_int32), ("num_classes", C.c_int32), ("sm_dim", C.c_int32), ("lg_dim", C.c_int32),
@@ -361,6 +371,26 @@ SYMBOLS: List[Tuple[str, object, list]] = [
     ("vitx_crossformer_read", C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, _P(C.c_int64)]),
     ("vitx_crossformer_partition", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 6),
     ("vitx_crossformer_window_attn", C.c_int32, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_float, C.c_int32] + [C.c_void_p] * 3),
+    ("vitx_regionvit_param_table_size", C.c_int32, [_P(RegionViTConfig), _P(C.c_int64), _P(C.c_int64)]),
+    ("vitx_regionvit_param_table_entry", C.c_int32,
+     [_P(RegionViTConfig), C.c_int64, C.c_char_p, C.c_int32, _P(C.c_int64), _P(C.c_int32), _P(C.c_int64)]),
+    ("vitx_regionvit_create", C.c_int32, [_P(RegionViTConfig), _P(C.c_void_p)]),
+    ("vitx_regionvit_destroy", C.c_int32, [C.c_void_p]),
+    ("vitx_regionvit_set_params", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_regionvit_get_params", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_regionvit_get_grads", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_regionvit_params_dev", C.c_int32, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)]),
+    ("vitx_regionvit_grads_dev", C.c_int32, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)]),
+    ("vitx_regionvit_params_changed", C.c_int32, [C.c_void_p]),
+    ("vitx_regionvit_forward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("vitx_regionvit_forward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("vitx_regionvit_backward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("vitx_regionvit_backward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("vitx_regionvit_profile_begin", C.c_int32, [C.c_void_p]),
+    ("vitx_regionvit_profile_end", C.c_int32, [C.c_void_p, _P(KernelStat), C.c_int32, _P(C.c_int32)]),
+    ("vitx_regionvit_read", C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, _P(C.c_int64)]),
+    ("vitx_regionvit_attn", C.c_int32, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_float, C.c_int32] + [C.c_void_p] * 4),
+    ("vitx_regionvit_partition", C.c_int32, [C.c_void_p] * 4 + [C.c_int32] * 7),
 ]
 
 _lib = None
@@ -437,6 +467,11 @@ def cvt_param_table(cfg: CvTConfig):
 def crossformer_param_table(cfg: CrossFormerConfig):
     """[(name, shape, offset)] of CrossFormer's variables from the C library (host-only call; no GPU needed)."""
     return table_of("vitx_crossformer", C.byref(cfg))
+
+
+def regionvit_param_table(cfg: RegionViTConfig):
+    """[(name, shape, offset)] of RegionViT's variables from the C library (host-only call; no GPU needed)."""
+    return table_of("vitx_regionvit", C.byref(cfg))
 
 
 def mim_param_table(handle, prefix="vitx_mim"):
