@@ -822,6 +822,70 @@ int32_t vitx_regionvit_attn(vitx_regionvit_handle m, const float* qkv_host, cons
 int32_t vitx_regionvit_partition(vitx_regionvit_handle m, float* region_host, float* local_host, float* tokens_host, int32_t b, int32_t rh, int32_t rw,
                                  int32_t wh, int32_t ww, int32_t c, int32_t inverse);
 
+/* ---- PiT (pit.py:158-219): Unfold(patch_size, stride patch_size // 2) + Dense (:110-122,179-182: overlapping 'VALID' patches in (kh, kw, c)
+ * order), the class token and the position rows (:211-213), one Transformer (:91-108) per entry of zip(depth, heads) -- pre-norm Attention
+ * (heads of dim_head, to_out absent when heads == 1 and dim_head == dim, :59) and MLP -- and LayerNormalization + Dense on row 0
+ * (:202-205,217).  Each stage with layers runs on one ordinary vitx_config engine (VITX_VARIANT_VIT), so vitx_pit_set_long_attn applies.
+ * pit.py:194 `not_last = ind < (len(depth) < 1)` is never true: the reference never inserts its Pool (:140-156) and never doubles dim.
+ * pool_stages == 0 reproduces that.  pool_stages != 0 runs the loop body of :196-200 with not_last true: behind every stage but the last a
+ * Pool(dim) -- Dense dim -> 2 dim on the class row (:148), Conv2D(2 dim, 3, strides 2, 'SAME', groups = dim) with bias and a 1x1 Conv2D with
+ * bias (:130-131) on the other rows as a square map -- and dim doubled; mlp_dim and dim_head stay.  A handle of its own; parameter order in
+ * DESIGN.md section 27.  Only the deterministic path (dropout 0) exists. */
+#define VITX_PIT_MAX_STAGES 8
+typedef struct vitx_pit_config {
+  /* the image the handle is built for; both 0 is allowed for the host-only table calls */
+  int32_t image_h, image_w;
+  int32_t image_size;               /* pit.py:160: sizes pos_embedding [1, conv_output_size(image_size, patch_size, patch_size // 2)^2 + 1, dim] (:184-187) */
+  int32_t patch_size;               /* :161 */
+  int32_t num_classes;              /* :162 */
+  int32_t dim;                      /* :163 */
+  int32_t n_stages;                 /* the length of zip(depth, cast_tuple(heads, len(depth))) (:177,193) */
+  int32_t depth[VITX_PIT_MAX_STAGES], heads[VITX_PIT_MAX_STAGES];   /* :164-165; a depth of 0 is a stage without layers */
+  int32_t mlp_dim, dim_head;        /* :166-167 */
+  int32_t pool_stages;              /* 0: the reference (no Pool); != 0: Pool(dim) behind every stage but the last */
+  float ln_eps;                     /* <= 0: Keras LayerNormalization's 1e-3 */
+  int32_t compute;                  /* VITX_COMPUTE_*: the transformer blocks' mode; tokenizer, Pool and head keep fp32 storage */
+  int32_t max_batch;
+  int32_t device_id;
+  int32_t long_attn;                /* != 0: vitx_pit_set_long_attn(handle, 1) at creation */
+  int32_t reserved[8];
+} vitx_pit_config;
+typedef struct vitx_pit* vitx_pit_handle;
+/* host only, no GPU needed */
+int32_t vitx_pit_param_table_size(const vitx_pit_config* cfg, int64_t* n_tensors, int64_t* n_elems);
+int32_t vitx_pit_param_table_entry(const vitx_pit_config* cfg, int64_t index, char* name, int32_t name_cap, int64_t shape[4], int32_t* rank,
+                                   int64_t* offset_elems);
+int32_t vitx_pit_create(const vitx_pit_config* cfg, vitx_pit_handle* out);
+int32_t vitx_pit_destroy(vitx_pit_handle m);
+int32_t vitx_pit_set_params(vitx_pit_handle m, const float* host_blob, int64_t n_elems);
+int32_t vitx_pit_get_params(vitx_pit_handle m, float* host_blob, int64_t n_elems);
+int32_t vitx_pit_get_grads(vitx_pit_handle m, float* host_blob, int64_t n_elems);
+int32_t vitx_pit_params_dev(vitx_pit_handle m, float** dev_ptr, int64_t* n_elems);
+int32_t vitx_pit_grads_dev(vitx_pit_handle m, float** dev_ptr, int64_t* n_elems);
+int32_t vitx_pit_params_changed(vitx_pit_handle m);
+/* vitx_set_long_attn on every stage's engine (the streamed-key attention past 288 tokens; bf16, dim_head 64); the first refusal is returned */
+int32_t vitx_pit_set_long_attn(vitx_pit_handle m, int32_t on);
+/* PiT.call (pit.py:207-219).  img [b, image_h, image_w, 3] NHWC; logits [b, num_classes] */
+int32_t vitx_pit_forward(vitx_pit_handle m, const float* img_host, int32_t b, float* logits_host);
+int32_t vitx_pit_forward_dev(vitx_pit_handle m, const float* img_dev, int32_t b, float* logits_dev_or_null);
+/* VJP of the last forward for d(logits): overwrites the gradient arena (pos_embedding rows the image does not use: zeros); d(img) only when
+ * asked for */
+int32_t vitx_pit_backward(vitx_pit_handle m, const float* dlogits_host, float* dimg_host_or_null);
+int32_t vitx_pit_backward_dev(vitx_pit_handle m, const float* dlogits_dev, float* dimg_dev_or_null);
+/* Pool.call (pit.py:146-156) of the Pool behind `stage` alone, on host tokens [b, n, dim_stage] with n = 1 + h * h at most the stage's own token
+ * count: out [b, 1 + ceil(h / 2)^2, 2 dim_stage].  A handle whose stages all have depth 0 is one of pools alone.  pool_backward is the VJP of
+ * the last pool_forward: dout as out; it writes that Pool's six entries of the gradient arena (vitx_pit_get_grads) and, when asked for,
+ * d(tokens).  Both invalidate the state of a model forward. */
+int32_t vitx_pit_pool_forward(vitx_pit_handle m, int32_t stage, const float* tokens_host, int32_t b, int32_t n, float* out_host);
+int32_t vitx_pit_pool_backward(vitx_pit_handle m, int32_t stage, const float* dout_host, float* dtokens_host_or_null);
+/* per-kernel-class timing as vitx_profile_begin / _end: every engine's block classes plus the composite's own (pit_unfold, pit_embed,
+ * pit_pool_fwd, pit_pool_bwd, pit_head).  A handle without an engine profiles nothing. */
+int32_t vitx_pit_profile_begin(vitx_pit_handle m);
+int32_t vitx_pit_profile_end(vitx_pit_handle m, vitx_kernel_stat* out, int32_t cap, int32_t* n_out);
+/* "tokens" [b, n_0, dim] (behind the position rows), "stage.<s>" [b, n_s, dim_s] (the stage's output), "pooled.<s>" [b, n_{s+1}, 2 dim_s] (the
+ * Pool behind stage s) */
+int32_t vitx_pit_read(vitx_pit_handle m, const char* which, float* out_host, int64_t cap_elems, int64_t* n_elems);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libvitx.so")
-SOURCES = ["env.hip", "elementwise.hip", "gemm_generic.hip", "gemm_f32_mfma.hip", "gemm_bf16x3.hip", "gemm_bf16.hip", "gemm_bf16_pipe.hip", "gemm_bf16_tn.hip", "attn_bf16.hip", "attn_stream.hip", "attn_x3.hip", "attn_generic.hip", "attn_lsa.hip", "attn_fewkey.hip", "attn_window.hip", "spt.hip", "attn_bgemm_mfma.hip", "attn_headchain.hip", "attn_deepvit_fused.hip", "attn_cait_fused.hip", "mim_ops.hip", "mim.hip", "distill.hip", "cross_vit.hip", "cct_tok.hip", "cct.hip", "nest_ops.hip", "nest.hip", "twins_ops.hip", "twins.hip", "cvt_ops.hip", "cvt.hip", "crossformer_ops.hip", "crossformer.hip", "regionvit_ops.hip", "regionvit.hip", "comm.hip", "engine.hip", "capi.hip"]
+SOURCES = ["env.hip", "elementwise.hip", "gemm_generic.hip", "gemm_f32_mfma.hip", "gemm_bf16x3.hip", "gemm_bf16.hip", "gemm_bf16_pipe.hip", "gemm_bf16_tn.hip", "attn_bf16.hip", "attn_stream.hip", "attn_x3.hip", "attn_generic.hip", "attn_lsa.hip", "attn_fewkey.hip", "attn_window.hip", "spt.hip", "attn_bgemm_mfma.hip", "attn_headchain.hip", "attn_deepvit_fused.hip", "attn_cait_fused.hip", "mim_ops.hip", "mim.hip", "distill.hip", "cross_vit.hip", "cct_tok.hip", "cct.hip", "nest_ops.hip", "nest.hip", "twins_ops.hip", "twins.hip", "cvt_ops.hip", "cvt.hip", "crossformer_ops.hip", "crossformer.hip", "regionvit_ops.hip", "regionvit.hip", "pit_ops.hip", "pit.hip", "comm.hip", "engine.hip", "capi.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # per-source additions.  attn_bf16.hip / attn_x3.hip: the running row maxima come straight out of MFMA accumulators; with NaNs honoured every fmaxf first

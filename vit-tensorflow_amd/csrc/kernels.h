@@ -256,6 +256,27 @@ void launch_cvt_dw_bwd_dkern(const void* x, int is_bf16, const float* dconv, flo
 void launch_cvt_dw_bwd_dx(const float* dconv_q, const float* kern_q, const float* dconv_kv, const float* kern_kv, int st_kv, void* dx, int is_bf16, int b, int H,
                           int W, int C, int k, hipStream_t s);
 
+// ---------------------------------------------------------------- pit_ops.hip
+// PiT (pit.py) on fp32 token rows [b, 1 + h w, d], row 0 the class token; 32-bit index arithmetic: the caller checks pit_ops_fits(elements) of
+// every tensor it passes.  Buffers that feed a GEMM over token rows keep a row 0 of zeros per image.
+bool pit_ops_fits(int64_t elems);
+// Unfold (pit.py:110-122): rows [b, 1 + oh ow, Kp] (Kp a multiple of 4, columns past p p C zeros, row 0 zeros) of the p x p patches every st pixels
+// ('VALID') in (kh, kw, c) order; its VJP gathers for every pixel the patches that cover it (every element of dimg written once)
+void launch_pit_unfold(const float* img, float* rows, int b, int H, int W, int C, int p, int st, int oh, int ow, int Kp, hipStream_t s);
+void launch_pit_unfold_bwd(const float* drows, float* dimg, int b, int H, int W, int C, int p, int st, int oh, int ow, int Kp, hipStream_t s);
+// x[bi, 0] = cls + pos[0], x[bi, r] += pos[r] (pit.py:211-213); dpos [pos_rows, d] = the sum over the images of g (rows >= n zeros), dcls = dpos[0]
+void launch_pit_cls_pos(float* x, const float* cls, const float* pos, int b, int n, int d, hipStream_t s);
+void launch_pit_pos_grad(const float* g, float* dpos, float* dcls, int b, int n, int pos_rows, int d, hipStream_t s);
+// out[c] = sum over the images and the rows 1 .. ntok - 1 of v[bi, row, c], as fixed-slice partials (ws: pit_rowsum_ws_elems floats) added in order
+int64_t pit_rowsum_ws_elems(int C);
+void launch_pit_rowsum(const float* v, float* ws, float* out, int b, int ntok, int C, hipStream_t s);
+// Pool's depthwise Conv2D(2 d, 3, strides 2, 'SAME', groups = d) with bias (pit.py:130,143) on rows 1.. of x read as the h x w map: dw
+// [b, 1 + oh ow, 2 d] with row 0 zeros; d(kernel) [3, 3, 1, 2 d] and d(bias) from x and d(dw) (ws: pit_pool_ws_elems floats); rows 1.. of d(x)
+int64_t pit_pool_ws_elems(int d);
+void launch_pit_pool_dw_fwd(const float* x, const float* kern, const float* bias, float* dw, int b, int h, int w, int d, hipStream_t s);
+void launch_pit_pool_dw_bwd_params(const float* x, const float* ddw, float* ws, float* dkern, float* dbias, int b, int h, int w, int d, hipStream_t s);
+void launch_pit_pool_dw_bwd_dx(const float* ddw, const float* kern, float* dx, int b, int h, int w, int d, hipStream_t s);
+
 // ---------------------------------------------------------------- elementwise.hip
 void launch_unfold(const float* img, void* out, int out_bf16, int b, int H, int W, int C, int ph, int pw,
                    int64_t ldo, hipStream_t s);

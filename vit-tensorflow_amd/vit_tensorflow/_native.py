@@ -167,6 +167,23 @@ class CrossViTConfig(C.Structure):
     ]
 
 
+PIT_MAX_STAGES = 8
+
+
+class PiTConfig(C.Structure):
+    _fields_ = [
+        ("image_h", C.c_int32), ("image_w", C.c_int32), ("image_size", C.c_int32), ("patch_size", C.c_int32), ("num_classes", C.c_int32),
+        ("dim", C.c_int32), ("n_stages", C.c_int32), ("depth", C.c_int32 * PIT_MAX_STAGES), ("heads", C.c_int32 * PIT_MAX_STAGES),
+        ("mlp_dim", C.c_int32), ("dim_head", C.c_int32), ("pool_stages", C.c_int32),
+        ("ln_eps", C.c_float),
+        ("compute", C.c_int32),
+        ("max_batch", C.c_int32),
+        ("device_id", C.c_int32),
+        ("long_attn", C.c_int32),
+        ("reserved", C.c_int32 * 8),
+    ]
+
+
 GRAD_READY_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64, C.c_int64)
 
 # every symbol include/vitx.h declares: (name, restype, argtypes)
@@ -391,6 +408,26 @@ SYMBOLS: List[Tuple[str, object, list]] = [
     ("vitx_regionvit_read", C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, _P(C.c_int64)]),
     ("vitx_regionvit_attn", C.c_int32, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_float, C.c_int32] + [C.c_void_p] * 4),
     ("vitx_regionvit_partition", C.c_int32, [C.c_void_p] * 4 + [C.c_int32] * 7),
+    ("vitx_pit_param_table_size", C.c_int32, [_P(PiTConfig), _P(C.c_int64), _P(C.c_int64)]),
+    ("vitx_pit_param_table_entry", C.c_int32, [_P(PiTConfig), C.c_int64, C.c_char_p, C.c_int32, _P(C.c_int64), _P(C.c_int32), _P(C.c_int64)]),
+    ("vitx_pit_create", C.c_int32, [_P(PiTConfig), _P(C.c_void_p)]),
+    ("vitx_pit_destroy", C.c_int32, [C.c_void_p]),
+    ("vitx_pit_set_params", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_pit_get_params", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_pit_get_grads", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("vitx_pit_params_dev", C.c_int32, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)]),
+    ("vitx_pit_grads_dev", C.c_int32, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)]),
+    ("vitx_pit_params_changed", C.c_int32, [C.c_void_p]),
+    ("vitx_pit_set_long_attn", C.c_int32, [C.c_void_p, C.c_int32]),
+    ("vitx_pit_forward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("vitx_pit_forward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("vitx_pit_backward", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("vitx_pit_backward_dev", C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("vitx_pit_pool_forward", C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    ("vitx_pit_pool_backward", C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("vitx_pit_profile_begin", C.c_int32, [C.c_void_p]),
+    ("vitx_pit_profile_end", C.c_int32, [C.c_void_p, _P(KernelStat), C.c_int32, _P(C.c_int32)]),
+    ("vitx_pit_read", C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, _P(C.c_int64)]),
 ]
 
 _lib = None
@@ -472,6 +509,11 @@ def crossformer_param_table(cfg: CrossFormerConfig):
 def regionvit_param_table(cfg: RegionViTConfig):
     """[(name, shape, offset)] of RegionViT's variables from the C library (host-only call; no GPU needed)."""
     return table_of("vitx_regionvit", C.byref(cfg))
+
+
+def pit_param_table(cfg: PiTConfig):
+    """[(name, shape, offset)] of PiT's variables from the C library (host-only call; no GPU needed)."""
+    return table_of("vitx_pit", C.byref(cfg))
 
 
 def mim_param_table(handle, prefix="vitx_mim"):
