@@ -872,7 +872,7 @@ int32_t vitx_debug_read(vitx_handle h, const char* which, int32_t layer, float* 
     else if (w == "mean2") { src = ba.mean2; cols = ld = 1; }
     else if (w == "rstd2") { src = ba.rstd2; cols = ld = 1; }
     else if (w == "lse") {   // [b, heads, n] as the fused and streamed attention kernels save it; the other attention forms keep another record (or none)
-      if (ba.lse_bhn) { src = ba.lse; rows = (int64_t)b * c.heads; cols = ld = nq; }
+      if (lse_is_bhn(ba)) { src = ba.lse; rows = (int64_t)b * c.heads; cols = ld = nq; }
     }
     else if (w == "d_hpre" || w == "d_attn_out" || w == "d_qkv" || w == "d_y1") {
       // intermediates of the backward: handle-level buffers that hold the block whose backward ran last, and only in the layouts recorded there

@@ -72,6 +72,9 @@ struct BlockParams {
   int64_t p_begin = 0, p_end = 0;   // arena range of this block's parameters
 };
 
+// the attention kernel families (engine.hip: select_attn_path chooses one per block forward, in this order); Generic: the materialised path
+enum class AttnPath { Lsa, Window, Small, X3, Fused, Stream, FewKey, ManyKey, Generic };
+
 struct BlockActs {
   float *x_in = nullptr, *x_mid = nullptr, *x_out = nullptr;
   void *y1 = nullptr, *qkv = nullptr, *q = nullptr, *kv = nullptr, *ctx = nullptr, *o = nullptr, *fa = nullptr;
@@ -94,10 +97,11 @@ struct BlockActs {
   int sc_pi = 0;                    // index of the tensor that multiplies V
   bool sc_no_mixed = false;         // kept by the one-kernel DeepViT forward: sc_keep[1] (the mixed scores) was not written
   bool sc_a2_bf16 = false;   // sc_keep[2] holds bf16 [nq][round_up(nk, 8)] planes (one-kernel forward with the one-kernel backward as its reader)
-  bool lse_bhn = false;             // the last forward of this block ran the fused or the streamed-key attention on every row: lse holds [b, heads, n] (vitx_debug_read)
-  bool attn_streamed = false;       // the last forward of this block ran the streamed-key attention (attn_stream.hip): its backward does too
+  AttnPath attn_path = AttnPath::Generic;   // the path the last forward of this block took (attn_forward): its backward takes the same one
+  bool attn_cls_rows = false;       // ... in the class-row form of the Fused path (query row 0 of every image only)
   int par_first = 0, par_last = 0;   // backward order inside a group of parallel half-blocks: first / last one processed (1 + 1 = alone)
 };
+inline bool lse_is_bhn(const BlockActs& ba) { return (ba.attn_path == AttnPath::Fused && !ba.attn_cls_rows) || ba.attn_path == AttnPath::Stream; }   // lse holds [b, heads, n] (vitx_debug_read)
 
 // Class-row form of the last block (engine.hip, block_forward_cls_rows): under cls pooling the head reads row 0 of every image only, so everything of
 // the last block behind its attention runs on the b class rows, gathered into these compact [b, *] buffers.  The bf16 ones are A / K operands of

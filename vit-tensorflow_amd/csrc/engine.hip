@@ -770,6 +770,34 @@ struct AttnView {   // per-head-addressable views into [b, n, (h d)]-style tenso
   void* o = nullptr; int64_t ldo = 0, ob = 0;
   int nq = 0, nk = 0;
 };
+struct AttnGrad {   // gradients, same addressing conventions as AttnView
+  const void* d_o = nullptr; int64_t ldo = 0, ob = 0;
+  void *dq = nullptr, *dk = nullptr, *dv = nullptr;
+  int64_t lddq = 0, lddk = 0, lddv = 0, dqb = 0, dkb = 0, dvb = 0;
+};
+// The two layouts q, k and v come in (a.nq and a.nk are set by the caller).  Packed: column blocks of one [b nq, 3 inner] matrix (vit.py:73, CaiT's
+// concatenated patch stage).  Split: q [b nq, inner] and k | v as the column blocks of kv [b nk, 2 inner] (cait.py:116, cvt.py:116, twins_svt.py:181).
+static void packed_qkv_view(AttnView& a, const void* qkv, int inner, int esz) {
+  a.q = qkv; a.k = boff(qkv, inner, esz); a.v = boff(qkv, 2 * inner, esz);
+  a.ldq = a.ldk = a.ldv = 3 * inner; a.qb = a.kb = a.vb = (int64_t)a.nq * 3 * inner;
+}
+static void split_qkv_view(AttnView& a, const void* q, const void* kv, int inner, int esz) {
+  a.q = q; a.ldq = inner; a.qb = (int64_t)a.nq * inner;
+  a.k = kv; a.v = boff(kv, inner, esz); a.ldk = a.ldv = 2 * inner; a.kb = a.vb = (int64_t)a.nk * 2 * inner;
+}
+// Their gradients live in d_qkv: [b nq, 3 inner] for the packed layout, [dq | dkv] for the split one.
+static void packed_qkv_grad(AttnGrad& g, const AttnView& a, void* dqkv, int inner, int esz) {
+  g.dq = dqkv; g.dk = boff(dqkv, inner, esz); g.dv = boff(dqkv, 2 * inner, esz);
+  g.lddq = g.lddk = g.lddv = 3 * inner; g.dqb = g.dkb = g.dvb = (int64_t)a.nq * 3 * inner;
+}
+// Element offset of dkv [b nk, 2 inner] behind dq [rows, inner].  dq is the K operand of the to_q weight gradient and keeps the row padding of every
+// such operand, round_up(rows, 256) + 320 zero-filled rows in all (the 320 are what the GEMM tiles may read past the 256-row multiple: e->mp); dkv
+// starts behind them.  d_qkv is sized for it: the (rmax + 256) * 3 inner of the packed form hold the padded dq, crow_max * 2 inner more the dkv.
+static int64_t dkv_offset(int64_t rows, int inner) { return (round_up(rows, 256) + 320) * inner; }
+static void split_qkv_grad(AttnGrad& g, const AttnView& a, void* dqkv, int64_t rows, int inner, int esz) {
+  g.dq = dqkv; g.lddq = inner; g.dqb = (int64_t)a.nq * inner;
+  g.dk = boff(dqkv, dkv_offset(rows, inner), esz); g.dv = boff(g.dk, inner, esz); g.lddk = g.lddv = 2 * inner; g.dkb = g.dvb = (int64_t)a.nk * 2 * inner;
+}
 
 static int ensure_scores(vitx_engine* e, int count, int64_t elems, std::string& err) {
   if (elems > e->sc_elems) {
@@ -923,12 +951,6 @@ static void attn_generic_fwd(vitx_engine* e, const BlockParams& bp, const AttnVi
   bgemm(e, sc[pi], 0, ld, 1, bs, hs, a.v, T, a.ldv, 1, a.vb, dh, a.nq, dh, a.nk, b, h, EPI_STORE, T, a.o, a.ldo, a.ob, dh, 1.0f);
 }
 
-struct AttnGrad {   // gradients, same addressing conventions as AttnView
-  const void* d_o = nullptr; int64_t ldo = 0, ob = 0;
-  void *dq = nullptr, *dk = nullptr, *dv = nullptr;
-  int64_t lddq = 0, lddk = 0, lddv = 0, dqb = 0, dkb = 0, dvb = 0;
-};
-
 static void attn_generic_bwd(vitx_engine* e, const BlockParams& bp, const AttnView& a, const AttnGrad& gr, int b, BlockActs* keep) {
   const int h = e->cfg.heads, dh = e->cfg.dim_head, T = e->bf16;
   const int64_t ld = round_up(a.nk, 4);
@@ -1062,6 +1084,154 @@ static bool use_fused_attn_x3(const vitx_engine* e, int n) {
          attn_x3_supported(n, e->cfg.dim_head);
 }
 
+// The attention path of one block forward: the only caller of the predicates above.  attn_forward saves the result in BlockActs::attn_path and
+// attn_backward switches on the saved value, so a flag switched between the two passes (vitx_set_long_attn) cannot part them.  The order is the
+// precedence.  (A bias takes Window only where Small would serve it too: attn_forward refuses a bias that neither serves.)
+//
+// Which paths the q / k / v layouts of block_forward / block_backward reach, beside Generic, which every layout runs:
+//   packed [q | k | v]        Lsa, Window, Small, X3, Fused, Stream.  None of them is reached from another layout: Small (and with it Window), X3,
+//                             Fused and Stream test !reduced_keys and nest_block or the ViT variant; Lsa needs small_dataset, which build_param_table
+//                             refuses on another variant ("small_dataset needs the ViT variant") and with the nest_block that reduced keys need
+//   CaiT, concatenated, split none: the above, and FewKey / ManyKey need global_k or conv_proj_kernel, refused without nest_block, itself refused on
+//                             another variant ("nest_block needs the ViT variant")
+//   conv_proj (split)         FewKey, ManyKey: both test their layout's own switch (reduced_keys, conv_proj_kernel), so the packed layout reaches neither
+//   global_k (split)          FewKey; not ManyKey ("conv_proj_kernel does not combine with global_k")
+static AttnPath select_attn_path(const vitx_engine* e, int l, int b, int nq, int nk) {
+  if (e->cfg.small_dataset) return AttnPath::Lsa;   // vit_for_small_dataset.py:109-117
+  if (!e->attn_bias.empty() && e->attn_bias[(size_t)l] && use_small_attn(e, nq) && use_window_attn(e, nq)) return AttnPath::Window;   // crossformer.py:156-171
+  if (use_small_attn(e, nq)) return AttnPath::Small;   // nest.py:101-105
+  if (use_fused_attn_x3(e, nq)) return AttnPath::X3;
+  if (use_fused_attn(e, nq)) return AttnPath::Fused;
+  if (use_stream_attn(e, nq)) return AttnPath::Stream;
+  if (use_fewkey_attn(e, b, nq, nk)) return AttnPath::FewKey;   // twins_svt.py:184-187
+  if (use_manykey_attn(e, b, nq, nk)) return AttnPath::ManyKey;   // cvt.py:120-123
+  return AttnPath::Generic;
+}
+// profiler classes of the paths' kernels, in the order of AttnPath (Generic books its launches one by one)
+static const char* const ATTN_FWD_CLASS[] = {"attn_lsa_fwd", "attn_window_fwd", "attn_small_fwd", "attn_x3_fwd", "attn_bf16_fwd", "attn_stream_fwd", "attn_fewkey_fwd", "attn_manykey_fwd"};
+static const char* const ATTN_BWD_CLASS[] = {"attn_lsa_bwd", "attn_window_bwd", "attn_small_bwd", "attn_x3_bwd", "attn_bf16_bwd", "attn_stream_bwd", "attn_fewkey_bwd", "attn_manykey_bwd"};
+static_assert(sizeof ATTN_FWD_CLASS == sizeof ATTN_BWD_CLASS && sizeof ATTN_FWD_CLASS / sizeof *ATTN_FWD_CLASS == (size_t)AttnPath::Generic && (int)AttnPath::ManyKey == 7,
+              "one class per path in front of Generic, in the order of AttnPath");
+
+// softmax(q k^T * scale [+ bias]) v of one block into a.o, on the path the selector names; what the backward needs stays in ba (lse, kept scores)
+// cls_rows: the class-row form of the Fused path (one live query row per image; the caller has checked cls_rows_apply)
+static int attn_forward(vitx_engine* e, Stage& st, int l, const AttnView& a, int b, bool cls_rows, std::string& err) {
+  const vitx_config& c = e->cfg;
+  const BlockParams& bp = st.bp[l];
+  BlockActs& ba = st.ba[l];
+  const int nq = a.nq, nk = a.nk, h = c.heads, dh = c.dim_head, inner = e->inner, T = e->bf16;
+  const float scale = 1.0f / std::sqrt((float)dh);
+  const float* attn_bias = e->attn_bias.empty() ? nullptr : e->attn_bias[(size_t)l];
+  const AttnPath path = select_attn_path(e, l, b, nq, nk);
+  // biased handles (crossformer.py:165): the BIAS form of the small-head kernels, or nothing -- the materialised path has not learnt the bias
+  if (attn_bias && (nq != e->attn_bias_n || dh != 32 || (path != AttnPath::Window && path != AttnPath::Small))) {
+    err = e->force_generic_attn ? "VITX_GENERIC_ATTN: the materialised attention path has no additive score bias; a biased (CrossFormer) handle runs the small-head kernels only"
+                                : "a biased attention handle needs dim_head 32 and sequences of exactly the bias's n <= 288 tokens";
+    return VITX_ERR_UNSUPPORTED;
+  }
+  if (path == AttnPath::Stream && !attn_stream_fits(b, nq, h)) { err = "long_attn: the streamed attention kernels take b * heads <= 65535 and n * 3 * heads * 64 < 2^30 elements per image"; return VITX_ERR_UNSUPPORTED; }
+  ba.attn_path = path;
+  ba.attn_cls_rows = path == AttnPath::Fused && cls_rows;
+  if (path == AttnPath::Generic) {
+    const int need = c.variant == VITX_VARIANT_VIT ? 1 : 3;
+    if (e->keep_scores && ba.sc_keep_elems == 0) {   // first use: this block's own score buffers, sized for the largest call
+      const int64_t emax = (int64_t)c.max_batch * h * st.nq_max * round_up(reduced_keys(c) ? global_keys(c) : st.nq_max + st.nc_max, 4);
+      if (e->sc_keep_bytes + need * emax * 4 <= e->sc_keep_budget) {
+        for (int i = 0; i < need; ++i) DALLOC(ba.sc_keep[i], (size_t)emax * 4, false);
+        ba.sc_keep_elems = emax;
+        e->sc_keep_bytes += need * emax * 4;
+      } else {
+        ba.sc_keep_elems = -1;
+      }
+    }
+    const int64_t elems = (int64_t)b * h * nq * round_up(nk, 4);
+    const bool keep = e->keep_scores && ba.sc_keep_elems >= elems;
+    if (!keep) {
+      ba.sc_geom = -1;
+      int rc = ensure_scores(e, need, elems, err);
+      if (rc != VITX_OK) return rc;
+    }
+    attn_generic_fwd(e, bp, a, b, keep ? &ba : nullptr);
+    return VITX_OK;
+  }
+  // one scope around the one launch: 4 flops per (query, key, feature); bytes: q, k, v and o of the packed layout, q, o and k | v of the split one
+  // (class-row form: one live query row per image -- q / o traffic and the products of one row, k and v of every row)
+  const bool split = path == AttnPath::FewKey || path == AttnPath::ManyKey;
+  const double live = ba.attn_cls_rows ? 1.0 / nq : 1.0, qb = (double)b * nq * inner * e->esz, kvb = (double)b * nk * 2 * inner * e->esz;
+  Prof pr(e, ATTN_FWD_CLASS[(int)path], 4.0 * b * h * (double)nq * nk * dh * live, split ? 2 * qb + kvb : qb * (2 + 2 * live));
+  switch (path) {
+  case AttnPath::Lsa: launch_attn_lsa_fwd(a.q, a.o, ba.lse, T, b, nq, h, dh, e->params + bp.temp, e->stream); break;   // learned temperature, masked diagonal
+  case AttnPath::Window: launch_attn_window_fwd((const bf16_t*)a.q, (bf16_t*)a.o, ba.lse, attn_bias, b, nq, h, scale, e->stream, e->attn_bias_hs); break;
+  case AttnPath::Small: launch_attn_small_fwd(a.q, a.o, ba.lse, T, b, nq, h, dh, scale, e->stream, attn_bias, e->attn_bias_hs); break;
+  case AttnPath::X3: launch_attn_x3_fwd((const float*)a.q, (float*)a.o, ba.lse, b, nq, h, scale, e->stream); break;
+  case AttnPath::Fused:
+    launch_attn_bf16_fwd((const bf16_t*)a.q, (bf16_t*)a.o, ba.lse, b, nq, h, scale, (const bf16_t*)e->zero_page, (e->reverse_mask >> 2) & 1, e->stream, cls_rows ? 1 : 0);
+    break;
+  case AttnPath::Stream: launch_attn_stream_fwd((const bf16_t*)a.q, (bf16_t*)a.o, ba.lse, b, nq, h, scale, e->stream); break;
+  case AttnPath::FewKey:
+    launch_attn_fewkey_fwd((const bf16_t*)a.q, (const bf16_t*)a.k, (bf16_t*)a.o, ba.lse, b, nq, nk, h, inner, 2 * inner, inner, scale, e->stream);
+    break;
+  case AttnPath::ManyKey:
+    launch_attn_manykey_fwd((const bf16_t*)a.q, (const bf16_t*)a.k, (bf16_t*)a.o, ba.lse, b, nq, nk, h, inner, 2 * inner, inner, scale, e->stream);
+    break;
+  case AttnPath::Generic: break;
+  }
+  return VITX_OK;
+}
+
+// The VJP of attn_forward on the path it saved: d(q, k, v) into g from g.d_o and the block's saved q, k, v, o and lse (or scores)
+static int attn_backward(vitx_engine* e, const BlockParams& bp, BlockActs& ba, int l, const AttnView& a, const AttnGrad& g, int b, std::string& err) {
+  const vitx_config& c = e->cfg;
+  const int nq = a.nq, nk = a.nk, h = c.heads, dh = c.dim_head, inner = e->inner, T = e->bf16;
+  const float scale = 1.0f / std::sqrt((float)dh);
+  const float* attn_bias = e->attn_bias.empty() ? nullptr : e->attn_bias[(size_t)l];
+  const AttnPath path = ba.attn_path;
+  if (path == AttnPath::Generic) {
+    int rc = ensure_scores(e, 4, (int64_t)b * h * nq * round_up(nk, 4), err);
+    if (rc != VITX_OK) return rc;
+    attn_generic_bwd(e, bp, a, g, b, &ba);
+  } else {
+    // flops: 14 per (query, key, feature), 10 on the few-key path; bytes: q, k, v, o, dO and d(q, k, v) of the packed layout, of the split ones q, o,
+    // dO, dq and twice k | v and dkv, the many-key kernels with three more passes over the queries and one more over the keys
+    // (class-row form: q, o, dO of one row per image; k, v read and d(q, k, v) written for every row)
+    const double pts = (double)b * h * nq * nk * dh, live = ba.attn_cls_rows ? 1.0 / nq : 1.0;
+    const double qb = (double)b * nq * inner * e->esz, kvb = (double)b * nk * 2 * inner * e->esz;
+    Prof pr(e, ATTN_BWD_CLASS[(int)path], (path == AttnPath::FewKey ? 10.0 : 14.0) * pts * live,
+            path == AttnPath::FewKey ? 4 * qb + 2 * kvb : path == AttnPath::ManyKey ? 7 * qb + 3 * kvb : qb * (5 + 3 * live));
+    switch (path) {
+    case AttnPath::Lsa:
+      launch_attn_lsa_bwd(a.q, a.o, g.d_o, ba.lse, e->dsum, g.dq, T, b, nq, h, dh, e->params + bp.temp, e->grads + bp.temp, e->lsa_ws, e->stream);
+      break;
+    case AttnPath::Window:
+      launch_attn_window_bwd((const bf16_t*)a.q, (const bf16_t*)a.o, (const bf16_t*)g.d_o, ba.lse, (bf16_t*)g.dq, attn_bias, b, nq, h, scale, e->stream, e->attn_bias_hs);
+      break;
+    case AttnPath::Small: launch_attn_small_bwd(a.q, a.o, g.d_o, ba.lse, e->dsum, g.dq, T, b, nq, h, dh, scale, e->stream, attn_bias, e->attn_bias_hs); break;
+    case AttnPath::X3: launch_attn_x3_bwd((const float*)a.q, (const float*)a.o, (const float*)g.d_o, ba.lse, (float*)g.dq, b, nq, h, scale, e->stream); break;
+    case AttnPath::Fused:
+      launch_attn_bf16_bwd((const bf16_t*)a.q, (const bf16_t*)a.o, (const bf16_t*)g.d_o, ba.lse, e->dsum, (bf16_t*)g.dq, b, nq, h, scale,
+                           (const bf16_t*)e->zero_page, e->stream, ba.attn_cls_rows ? 1 : 0);
+      break;
+    case AttnPath::Stream:
+      launch_attn_stream_bwd((const bf16_t*)a.q, (const bf16_t*)a.o, (const bf16_t*)g.d_o, ba.lse, e->dsum, (bf16_t*)g.dq, b, nq, h, scale, e->stream);
+      break;
+    case AttnPath::FewKey:
+      launch_attn_fewkey_bwd((const bf16_t*)a.q, (const bf16_t*)a.k, (const bf16_t*)a.o, (const bf16_t*)g.d_o, ba.lse, (bf16_t*)g.dq, (bf16_t*)g.dk, b, nq, nk,
+                             h, inner, 2 * inner, inner, inner, inner, 2 * inner, scale, e->stream);
+      break;
+    case AttnPath::ManyKey:
+      launch_attn_manykey_bwd((const bf16_t*)a.q, (const bf16_t*)a.k, (const bf16_t*)a.o, (const bf16_t*)g.d_o, ba.lse, (bf16_t*)g.dq, (bf16_t*)g.dk, b, nq, nk,
+                              h, inner, 2 * inner, inner, inner, inner, 2 * inner, scale, e->stream);
+      break;
+    case AttnPath::Generic: break;
+    }
+  }
+  if (e->attn_dbias && !e->attn_bias.empty()) {   // regionvit.py:107 -- the bias is a variable: d(bias) = sum over the sequences of dS
+    Prof pr(e, "attn_dbias", 4.0 * b * h * (double)nq * nq * dh, (double)b * nq * inner * 5 * e->esz);
+    launch_attn_dbias(a.q, a.o, g.d_o, ba.lse, T, b, nq, h, scale, attn_bias, e->attn_bias_hs, e->attn_dbias_ws, e->attn_dbias, e->stream);
+  }
+  return VITX_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // class-row form of the last block (vit.py:170: `x[:, 0]` is all the head reads under pool = 'cls')
 // ------------------------------------------------------------------------------------------------
@@ -1070,8 +1240,10 @@ static bool use_fused_attn_x3(const vitx_engine* e, int n) {
 // computes query row 0 of every image, and everything behind it runs on the b class rows, gathered into compact buffers (ClsRows).  Every Dense adds
 // its K terms in the same order whatever M is, so the logits have the bits of the full form.  VITX_LAST_BLOCK_FULL=1 (read per forward) keeps the
 // full form.
-static bool cls_rows_apply(const vitx_engine* e, int ntok, int extra, float drop) {
-  if (!e->cls_rows_ok || extra || drop > 0.f || !use_fused_attn(e, ntok)) return false;
+// (cls_rows_ok admits no path in front of Fused: it wants bf16 storage, which X3 has not, and neither small_dataset [Lsa] nor nest_block [Small,
+// and Window, which asks for Small's conditions too].)
+static bool cls_rows_apply(const vitx_engine* e, int b, int ntok, int extra, float drop) {
+  if (!e->cls_rows_ok || extra || drop > 0.f || select_attn_path(e, e->stages[0].depth - 1, b, ntok, ntok) != AttnPath::Fused) return false;
   return !vitx_env_flag("VITX_LAST_BLOCK_FULL");
 }
 // fc1 + GELU of the b class rows, with the GELU rounding the full launch gives exactly those rows.  The epilogue is not the same function of the
@@ -1165,9 +1337,7 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
   if (c.variant == VITX_VARIANT_CAIT && bp.qkvcat.wt) {
     EpiParams ep; ep.out = ba.qkv; ep.ldo = 3 * inner;
     dense_fwd(e, ba.y1, d, rows, bp.qkvcat, EPI_STORE, ep);                  // cait.py:114-115 with context = x: q and kv of the same tokens, one launch
-    av.q = ba.qkv; av.k = boff(ba.qkv, inner, esz); av.v = boff(ba.qkv, 2 * inner, esz);
-    av.ldq = av.ldk = av.ldv = 3 * inner;
-    av.qb = av.kb = av.vb = (int64_t)nq * 3 * inner;
+    packed_qkv_view(av, ba.qkv, inner, esz);
   } else if (c.variant == VITX_VARIANT_CAIT) {
     EpiParams ep; ep.out = ba.q; ep.ldo = inner;
     dense_fwd(e, ba.y1, d, rows, bp.q, EPI_STORE, ep);                       // cait.py:114
@@ -1179,9 +1349,7 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
     }
     EpiParams ep2; ep2.out = ba.kv; ep2.ldo = 2 * inner;
     dense_fwd(e, ctx, d, b * nk, bp.kv, EPI_STORE, ep2);                      // cait.py:115
-    av.q = ba.q; av.ldq = inner; av.qb = (int64_t)nq * inner;
-    av.k = ba.kv; av.ldk = 2 * inner; av.kb = (int64_t)nk * 2 * inner;
-    av.v = boff(ba.kv, inner, esz); av.ldv = 2 * inner; av.vb = av.kb;       // cait.py:116
+    split_qkv_view(av, ba.q, ba.kv, inner, esz);                             // cait.py:116
   } else if (c.conv_proj_kernel) {
     {   // cvt.py:84-85 of to_q (stride 1) and of to_kv (stride conv_proj_stride): depthwise convolution + BatchNormalization of the normalised map
       Prof pr(e, "cvt_dwbn_fwd", 0, ((double)rows * d * 2 + (double)b * nk * d) * (esz + 8));
@@ -1195,9 +1363,7 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
     dense_fwd(e, ba.qin, d, rows, bp.q, EPI_STORE, ep);                      // cvt.py:86 of to_q
     EpiParams ep2; ep2.out = ba.kv; ep2.ldo = 2 * inner;
     dense_fwd(e, ba.ctx, d, b * nk, bp.kv, EPI_STORE, ep2);                   // :86 of to_kv
-    av.q = ba.q; av.ldq = inner; av.qb = (int64_t)nq * inner;
-    av.k = ba.kv; av.ldk = 2 * inner; av.kb = (int64_t)nk * 2 * inner;
-    av.v = boff(ba.kv, inner, esz); av.ldv = 2 * inner; av.vb = av.kb;       // :116
+    split_qkv_view(av, ba.q, ba.kv, inner, esz);                             // :116
   } else if (c.global_k) {
     EpiParams ep; ep.out = ba.q; ep.ldo = inner;
     dense_fwd(e, ba.y1, d, rows, bp.q, EPI_STORE, ep);                       // twins_svt.py:179
@@ -1207,79 +1373,13 @@ static int block_forward(vitx_engine* e, Stage& st, int si, int l, int b, int nq
     }
     EpiParams ep2; ep2.out = ba.kv; ep2.ldo = 2 * inner;
     dense_fwd(e, ba.ctx, bp.kv.in_k, b * nk, bp.kv, EPI_STORE, ep2);          // :180, the strided convolution as a Dense on the window rows
-    av.q = ba.q; av.ldq = inner; av.qb = (int64_t)nq * inner;
-    av.k = ba.kv; av.ldk = 2 * inner; av.kb = (int64_t)nk * 2 * inner;
-    av.v = boff(ba.kv, inner, esz); av.ldv = 2 * inner; av.vb = av.kb;       // :181
+    split_qkv_view(av, ba.q, ba.kv, inner, esz);                             // :181
   } else {
     EpiParams ep; ep.out = ba.qkv; ep.ldo = 3 * inner;
     dense_fwd(e, ba.y1, d, rows, bp.qkv, EPI_STORE, ep);                     // vit.py:72
-    av.q = ba.qkv; av.k = boff(ba.qkv, inner, esz); av.v = boff(ba.qkv, 2 * inner, esz);   // vit.py:73
-    av.ldq = av.ldk = av.ldv = 3 * inner;
-    av.qb = av.kb = av.vb = (int64_t)nq * 3 * inner;
+    packed_qkv_view(av, ba.qkv, inner, esz);                                 // vit.py:73
   }
-  // biased handles (crossformer.py:165): the BIAS form of the small-head kernels, or nothing -- the materialised path has not learnt the bias
-  const float* attn_bias = e->attn_bias.empty() ? nullptr : e->attn_bias[(size_t)l];
-  if (attn_bias && (nq != e->attn_bias_n || c.dim_head != 32 || !use_small_attn(e, nq))) {
-    err = e->force_generic_attn ? "VITX_GENERIC_ATTN: the materialised attention path has no additive score bias; a biased (CrossFormer) handle runs the small-head kernels only"
-                                : "a biased attention handle needs dim_head 32 and sequences of exactly the bias's n <= 288 tokens";
-    return VITX_ERR_UNSUPPORTED;
-  }
-  ba.attn_streamed = false;
-  ba.lse_bhn = false;
-  if (c.small_dataset) {   // LSA (vit_for_small_dataset.py:109-117): learned temperature, masked diagonal
-    Prof pr(e, "attn_lsa_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
-    launch_attn_lsa_fwd(ba.qkv, ba.o, ba.lse, T, b, nq, c.heads, c.dim_head, e->params + bp.temp, e->stream);
-  } else if (attn_bias && use_window_attn(e, nq)) {   // crossformer.py:156-171, tiny windows
-    Prof pr(e, "attn_window_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
-    launch_attn_window_fwd((const bf16_t*)ba.qkv, (bf16_t*)ba.o, ba.lse, attn_bias, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), e->stream, e->attn_bias_hs);
-  } else if (use_small_attn(e, nq)) {   // nest.py:101-105
-    Prof pr(e, "attn_small_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
-    launch_attn_small_fwd(ba.qkv, ba.o, ba.lse, T, b, nq, c.heads, c.dim_head, 1.0f / std::sqrt((float)c.dim_head), e->stream, attn_bias, e->attn_bias_hs);
-  } else if (use_fused_attn_x3(e, nq)) {
-    Prof pr(e, "attn_x3_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
-    launch_attn_x3_fwd((const float*)ba.qkv, (float*)ba.o, ba.lse, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), e->stream);
-  } else if (use_fused_attn(e, nq)) {
-    // (class-row form: one live query row per image -- q / o traffic and the products of one row, k and v of every row)
-    const double live = cls_rows ? 1.0 / nq : 1.0;
-    Prof pr(e, "attn_bf16_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head * live, (double)rows * inner * (2 + 2 * live) * esz);
-    ba.lse_bhn = !cls_rows;
-    launch_attn_bf16_fwd((const bf16_t*)ba.qkv, (bf16_t*)ba.o, ba.lse, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), (const bf16_t*)e->zero_page, (e->reverse_mask >> 2) & 1, e->stream,
-                         cls_rows ? 1 : 0);
-  } else if (use_stream_attn(e, nq)) {
-    if (!attn_stream_fits(b, nq, c.heads)) { err = "long_attn: the streamed attention kernels take b * heads <= 65535 and n * 3 * heads * 64 < 2^30 elements per image"; return VITX_ERR_UNSUPPORTED; }
-    Prof pr(e, "attn_stream_fwd", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 4 * esz);
-    ba.attn_streamed = true;
-    ba.lse_bhn = true;
-    launch_attn_stream_fwd((const bf16_t*)ba.qkv, (bf16_t*)ba.o, ba.lse, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), e->stream);
-  } else if (use_fewkey_attn(e, b, nq, nk)) {   // twins_svt.py:184-187
-    Prof pr(e, "attn_fewkey_fwd", 4.0 * b * c.heads * (double)nq * nk * c.dim_head, ((double)rows * inner * 2 + (double)b * nk * 2 * inner) * esz);
-    launch_attn_fewkey_fwd((const bf16_t*)ba.q, (const bf16_t*)ba.kv, (bf16_t*)ba.o, ba.lse, b, nq, nk, c.heads, inner, 2 * inner, inner,
-                           1.0f / std::sqrt((float)c.dim_head), e->stream);
-  } else if (use_manykey_attn(e, b, nq, nk)) {   // cvt.py:120-123
-    Prof pr(e, "attn_manykey_fwd", 4.0 * b * c.heads * (double)nq * nk * c.dim_head, ((double)rows * inner * 2 + (double)b * nk * 2 * inner) * esz);
-    launch_attn_manykey_fwd((const bf16_t*)ba.q, (const bf16_t*)ba.kv, (bf16_t*)ba.o, ba.lse, b, nq, nk, c.heads, inner, 2 * inner, inner,
-                            1.0f / std::sqrt((float)c.dim_head), e->stream);
-  } else {
-    const int need = c.variant == VITX_VARIANT_VIT ? 1 : 3;
-    if (e->keep_scores && ba.sc_keep_elems == 0) {   // first use: this block's own score buffers, sized for the largest call
-      const int64_t emax = (int64_t)c.max_batch * c.heads * st.nq_max * round_up(reduced_keys(c) ? global_keys(c) : st.nq_max + st.nc_max, 4);
-      if (e->sc_keep_bytes + need * emax * 4 <= e->sc_keep_budget) {
-        for (int i = 0; i < need; ++i) DALLOC(ba.sc_keep[i], (size_t)emax * 4, false);
-        ba.sc_keep_elems = emax;
-        e->sc_keep_bytes += need * emax * 4;
-      } else {
-        ba.sc_keep_elems = -1;
-      }
-    }
-    const int64_t elems = (int64_t)b * c.heads * nq * round_up(nk, 4);
-    const bool keep = e->keep_scores && ba.sc_keep_elems >= elems;
-    if (!keep) {
-      ba.sc_geom = -1;
-      int rc = ensure_scores(e, need, elems, err);
-      if (rc != VITX_OK) return rc;
-    }
-    attn_generic_fwd(e, bp, av, b, keep ? &ba : nullptr);
-  }
+  if (const int rc = attn_forward(e, st, l, av, b, cls_rows, err)) return rc;
   if (cls_rows) {
     block_forward_cls_rows(e, bp, ba, b, nq);
     return VITX_OK;
@@ -1568,51 +1668,42 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
     d_o = e->d_o;
   }
   side_rotate(e, e->rg_dqkv, e->d_qkv);   // d(q, k, v) of this block: the previous block's may still feed its weight gradient
+  if (c.conv_proj_kernel && e->bn_inference) { err = "the saved forward ran BatchNormalization on the moving statistics (inference): it has no VJP"; return VITX_ERR_UNSUPPORTED; }
+  // q, k, v as the forward laid them out, and d(q, k, v) in d_qkv: [rows, 3 inner] beside the packed layout, [dq | dkv] beside the split one
+  const bool cait = c.variant == VITX_VARIANT_CAIT, split = cait ? !bp.qkvcat.wt : reduced_keys(c);
   AttnView av;
   av.nq = nq; av.nk = nk; av.o = ba.o; av.ldo = inner; av.ob = (int64_t)nq * inner;
   AttnGrad ag;
   ag.d_o = d_o; ag.ldo = inner; ag.ob = (int64_t)nq * inner;
-  if (c.variant == VITX_VARIANT_CAIT && bp.qkvcat.wt) {
+  if (split) {
+    split_qkv_view(av, ba.q, ba.kv, inner, esz);
+    split_qkv_grad(ag, av, e->d_qkv, rows, inner, esz);
+  } else {
+    packed_qkv_view(av, ba.qkv, inner, esz);
+    packed_qkv_grad(ag, av, e->d_qkv, inner, esz);
+  }
+  if (const int rc = attn_backward(e, bp, ba, l, av, ag, b, err)) return rc;
+  const hipEvent_t fork_qkv = side_prefork(e);   // d(q, k, v) is complete
+  // to_q / to_kv VJPs of the split layouts: d(xq) through dq [rows, inner] into d_y, d(xkv [b nk, kin]) through dkv [b nk, 2 inner] into d_ctx
+  auto split_proj_bwd = [&](const void* xq, const void* xkv, int kin) {
+    EpiParams ep; ep.out = e->d_y; ep.ldo = d;
+    dense_dgrad(e, ag.dq, inner, rows, bp.q, EPI_STORE, ep);
+    dense_wgrad(e, xq, d, ag.dq, inner, rows, bp.q, fork_qkv);
+    EpiParams ep2; ep2.out = e->d_ctx; ep2.ldo = kin;
+    dense_dgrad(e, ag.dk, 2 * inner, b * nk, bp.kv, EPI_STORE, ep2);
+    dense_wgrad(e, xkv, kin, ag.dk, 2 * inner, b * nk, bp.kv, fork_qkv);
+    side_note_read(e, e->rg_dqkv);
+  };
+  if (cait && !split) {
     // patch stage, concatenated [to_q | to_kv] operands: d(q | k | v) rows as one matrix -> ONE input-gradient GEMM straight into d(y1) (no second
     // GEMM + add pass), two weight gradients reading their column blocks of it
-    av.q = ba.qkv; av.k = boff(ba.qkv, inner, esz); av.v = boff(ba.qkv, 2 * inner, esz);
-    av.ldq = av.ldk = av.ldv = 3 * inner;
-    av.qb = av.kb = av.vb = (int64_t)nq * 3 * inner;
-    ag.dq = e->d_qkv; ag.dk = boff(e->d_qkv, inner, esz); ag.dv = boff(e->d_qkv, 2 * inner, esz);
-    ag.lddq = ag.lddk = ag.lddv = 3 * inner;
-    ag.dqb = ag.dkb = ag.dvb = (int64_t)nq * 3 * inner;
-    int rc = ensure_scores(e, 4, (int64_t)b * c.heads * nq * round_up(nk, 4), err);
-    if (rc != VITX_OK) return rc;
-    attn_generic_bwd(e, bp, av, ag, b, &ba);
     EpiParams ep; ep.out = e->d_y; ep.ldo = d;
-    const hipEvent_t fork_qkv = side_prefork(e);                                // d(q | k | v) is complete
     dense_dgrad(e, e->d_qkv, 3 * inner, rows, bp.qkvcat, EPI_STORE, ep);
     dense_wgrad(e, ba.y1, d, ag.dq, 3 * inner, rows, bp.q, fork_qkv);
     dense_wgrad(e, ba.y1, d, ag.dk, 3 * inner, rows, bp.kv, fork_qkv);
     side_note_read(e, e->rg_dqkv);
-  } else if (c.variant == VITX_VARIANT_CAIT) {
-    av.q = ba.q; av.ldq = inner; av.qb = (int64_t)nq * inner;
-    av.k = ba.kv; av.ldk = 2 * inner; av.kb = (int64_t)nk * 2 * inner;
-    av.v = boff(ba.kv, inner, esz); av.ldv = 2 * inner; av.vb = av.kb;
-    // d_qkv buffer reused as [dq | dkv]: dq [rows, inner], then dkv [b*nk, 2*inner]
-    void* dq = e->d_qkv;
-    void* dkv = boff(e->d_qkv, (round_up((int64_t)rows, 256) + 320) * inner, esz);
-    ag.dq = dq; ag.lddq = inner; ag.dqb = (int64_t)nq * inner;
-    ag.dk = dkv; ag.lddk = 2 * inner; ag.dkb = (int64_t)nk * 2 * inner;
-    ag.dv = boff(dkv, inner, esz); ag.lddv = 2 * inner; ag.dvb = ag.dkb;
-    int rc = ensure_scores(e, 4, (int64_t)b * c.heads * nq * round_up(nk, 4), err);
-    if (rc != VITX_OK) return rc;
-    attn_generic_bwd(e, bp, av, ag, b, &ba);
-    // to_q / to_kv VJPs
-    const void* ctx = nc > 0 ? ba.ctx : ba.y1;
-    EpiParams ep; ep.out = e->d_y; ep.ldo = d;
-    const hipEvent_t fork_qkv = side_prefork(e);                                // dq and dkv are complete
-    dense_dgrad(e, dq, inner, rows, bp.q, EPI_STORE, ep);                       // d y1 (via q)
-    dense_wgrad(e, ba.y1, d, dq, inner, rows, bp.q, fork_qkv);
-    EpiParams ep2; ep2.out = e->d_ctx; ep2.ldo = d;
-    dense_dgrad(e, dkv, 2 * inner, b * nk, bp.kv, EPI_STORE, ep2);              // d ctx (via k, v)
-    dense_wgrad(e, ctx, d, dkv, 2 * inner, b * nk, bp.kv, fork_qkv);
-    side_note_read(e, e->rg_dqkv);
+  } else if (cait) {
+    split_proj_bwd(ba.y1, nc > 0 ? ba.ctx : ba.y1, d);
     Prof pr(e, "ctx_bwd", 0, 0);
     if (nc > 0) {
       side_rotate(e, e->rg_dbr, e->d_br);
@@ -1623,38 +1714,8 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
       launch_add_T(e->d_y, e->d_ctx, T, (int64_t)rows * d, e->stream);
     }
   } else if (c.conv_proj_kernel) {
-    if (e->bn_inference) { err = "the saved forward ran BatchNormalization on the moving statistics (inference): it has no VJP"; return VITX_ERR_UNSUPPORTED; }
-    av.q = ba.q; av.ldq = inner; av.qb = (int64_t)nq * inner;
-    av.k = ba.kv; av.ldk = 2 * inner; av.kb = (int64_t)nk * 2 * inner;
-    av.v = boff(ba.kv, inner, esz); av.ldv = 2 * inner; av.vb = av.kb;
-    // d_qkv buffer as [dq | dkv], as CaiT's: dq [rows, inner], then dkv [b * nk, 2 * inner]
-    void* dq = e->d_qkv;
-    void* dkv = boff(e->d_qkv, (round_up((int64_t)rows, 256) + 320) * inner, esz);
-    ag.dq = dq; ag.lddq = inner; ag.dqb = (int64_t)nq * inner;
-    ag.dk = dkv; ag.lddk = 2 * inner; ag.dkb = (int64_t)nk * 2 * inner;
-    ag.dv = boff(dkv, inner, esz); ag.lddv = 2 * inner; ag.dvb = ag.dkb;
-    if (use_fewkey_attn(e, b, nq, nk)) {
-      Prof pr(e, "attn_fewkey_bwd", 10.0 * b * c.heads * (double)nq * nk * c.dim_head, ((double)rows * inner * 4 + (double)b * nk * 4 * inner) * esz);
-      launch_attn_fewkey_bwd((const bf16_t*)ba.q, (const bf16_t*)ba.kv, (const bf16_t*)ba.o, (const bf16_t*)d_o, ba.lse, (bf16_t*)dq, (bf16_t*)dkv, b, nq, nk,
-                             c.heads, inner, 2 * inner, inner, inner, inner, 2 * inner, 1.0f / std::sqrt((float)c.dim_head), e->stream);
-    } else if (use_manykey_attn(e, b, nq, nk)) {
-      Prof pr(e, "attn_manykey_bwd", 14.0 * b * c.heads * (double)nq * nk * c.dim_head, ((double)rows * inner * 7 + (double)b * nk * 6 * inner) * esz);
-      launch_attn_manykey_bwd((const bf16_t*)ba.q, (const bf16_t*)ba.kv, (const bf16_t*)ba.o, (const bf16_t*)d_o, ba.lse, (bf16_t*)dq, (bf16_t*)dkv, b, nq, nk,
-                              c.heads, inner, 2 * inner, inner, inner, inner, 2 * inner, 1.0f / std::sqrt((float)c.dim_head), e->stream);
-    } else {
-      int rc = ensure_scores(e, 4, (int64_t)b * c.heads * nq * round_up(nk, 4), err);
-      if (rc != VITX_OK) return rc;
-      attn_generic_bwd(e, bp, av, ag, b, &ba);
-    }
     // pointwise VJPs: d(q_in) into d_y, d(kv_in) into d_ctx; then BatchNormalization and the depthwise convolutions back onto the map (cvt.py:84-86)
-    EpiParams ep; ep.out = e->d_y; ep.ldo = d;
-    const hipEvent_t fork_qkv = side_prefork(e);                                // dq and dkv are complete
-    dense_dgrad(e, dq, inner, rows, bp.q, EPI_STORE, ep);
-    dense_wgrad(e, ba.qin, d, dq, inner, rows, bp.q, fork_qkv);
-    EpiParams ep2; ep2.out = e->d_ctx; ep2.ldo = d;
-    dense_dgrad(e, dkv, 2 * inner, b * nk, bp.kv, EPI_STORE, ep2);
-    dense_wgrad(e, ba.ctx, d, dkv, 2 * inner, b * nk, bp.kv, fork_qkv);
-    side_note_read(e, e->rg_dqkv);
+    split_proj_bwd(ba.qin, ba.ctx, d);
     Prof pr(e, "cvt_dwbn_bwd", 0, ((double)rows * d * 3 + (double)b * nk * d * 2) * (esz + 8));
     const float* P = e->params;
     float* G = e->grads;
@@ -1665,81 +1726,13 @@ static int block_backward(vitx_engine* e, Stage& st, int si, int l, int b, int n
     launch_cvt_dw_bwd_dkern(ba.y1, T, e->cv_dkv, e->cv_ws, G + bp.ckv.dw, b, c.image_h, c.image_w, d, k, st, e->stream);
     launch_cvt_dw_bwd_dx(e->cv_dq, P + bp.cq.dw, e->cv_dkv, P + bp.ckv.dw, st, e->d_y, T, b, c.image_h, c.image_w, d, k, e->stream);
   } else if (c.global_k) {
-    av.q = ba.q; av.ldq = inner; av.qb = (int64_t)nq * inner;
-    av.k = ba.kv; av.ldk = 2 * inner; av.kb = (int64_t)nk * 2 * inner;
-    av.v = boff(ba.kv, inner, esz); av.ldv = 2 * inner; av.vb = av.kb;
-    // d_qkv buffer as [dq | dkv], as CaiT's: dq [rows, inner], then dkv [b * nk, 2 * inner]
-    void* dq = e->d_qkv;
-    void* dkv = boff(e->d_qkv, (round_up((int64_t)rows, 256) + 320) * inner, esz);
-    ag.dq = dq; ag.lddq = inner; ag.dqb = (int64_t)nq * inner;
-    ag.dk = dkv; ag.lddk = 2 * inner; ag.dkb = (int64_t)nk * 2 * inner;
-    ag.dv = boff(dkv, inner, esz); ag.lddv = 2 * inner; ag.dvb = ag.dkb;
-    if (use_fewkey_attn(e, b, nq, nk)) {
-      Prof pr(e, "attn_fewkey_bwd", 10.0 * b * c.heads * (double)nq * nk * c.dim_head, ((double)rows * inner * 4 + (double)b * nk * 4 * inner) * esz);
-      launch_attn_fewkey_bwd((const bf16_t*)ba.q, (const bf16_t*)ba.kv, (const bf16_t*)ba.o, (const bf16_t*)d_o, ba.lse, (bf16_t*)dq, (bf16_t*)dkv, b, nq, nk,
-                             c.heads, inner, 2 * inner, inner, inner, inner, 2 * inner, 1.0f / std::sqrt((float)c.dim_head), e->stream);
-    } else {
-      int rc = ensure_scores(e, 4, (int64_t)b * c.heads * nq * round_up(nk, 4), err);
-      if (rc != VITX_OK) return rc;
-      attn_generic_bwd(e, bp, av, ag, b, &ba);
-    }
     // to_q / to_kv VJPs: d(y1) through q, then the window rows' gradient folded back onto the map and added (twins_svt.py:179-180)
-    EpiParams ep; ep.out = e->d_y; ep.ldo = d;
-    const hipEvent_t fork_qkv = side_prefork(e);                                // dq and dkv are complete
-    dense_dgrad(e, dq, inner, rows, bp.q, EPI_STORE, ep);
-    dense_wgrad(e, ba.y1, d, dq, inner, rows, bp.q, fork_qkv);
-    EpiParams ep2; ep2.out = e->d_ctx; ep2.ldo = bp.kv.in_k;
-    dense_dgrad(e, dkv, 2 * inner, b * nk, bp.kv, EPI_STORE, ep2);
-    dense_wgrad(e, ba.ctx, bp.kv.in_k, dkv, 2 * inner, b * nk, bp.kv, fork_qkv);
-    side_note_read(e, e->rg_dqkv);
+    split_proj_bwd(ba.y1, ba.ctx, bp.kv.in_k);
     Prof pr(e, "global_kv_fold", 0, 3.0 * rows * d * esz);
     launch_twins_kfold_add(e->d_ctx, bp.kv.in_k, e->d_y, T, b, c.image_h, c.image_w, d, c.global_k, e->stream);
   } else {
-    av.q = ba.qkv; av.k = boff(ba.qkv, inner, esz); av.v = boff(ba.qkv, 2 * inner, esz);
-    av.ldq = av.ldk = av.ldv = 3 * inner;
-    av.qb = av.kb = av.vb = (int64_t)nq * 3 * inner;
-    ag.dq = e->d_qkv; ag.dk = boff(e->d_qkv, inner, esz); ag.dv = boff(e->d_qkv, 2 * inner, esz);
-    ag.lddq = ag.lddk = ag.lddv = 3 * inner;
-    ag.dqb = ag.dkb = ag.dvb = (int64_t)nq * 3 * inner;
-    if (c.small_dataset) {
-      Prof pr(e, "attn_lsa_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
-      launch_attn_lsa_bwd(ba.qkv, ba.o, d_o, ba.lse, e->dsum, e->d_qkv, T, b, nq, c.heads, c.dim_head, e->params + bp.temp, e->grads + bp.temp,
-                          e->lsa_ws, e->stream);
-    } else if (!e->attn_bias.empty() && use_window_attn(e, nq)) {
-      Prof pr(e, "attn_window_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
-      launch_attn_window_bwd((const bf16_t*)ba.qkv, (const bf16_t*)ba.o, (const bf16_t*)d_o, ba.lse, (bf16_t*)e->d_qkv, e->attn_bias[(size_t)l], b, nq, c.heads,
-                             1.0f / std::sqrt((float)c.dim_head), e->stream, e->attn_bias_hs);
-    } else if (use_small_attn(e, nq)) {
-      Prof pr(e, "attn_small_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
-      launch_attn_small_bwd(ba.qkv, ba.o, d_o, ba.lse, e->dsum, e->d_qkv, T, b, nq, c.heads, c.dim_head, 1.0f / std::sqrt((float)c.dim_head), e->stream,
-                            e->attn_bias.empty() ? nullptr : e->attn_bias[(size_t)l], e->attn_bias_hs);
-    } else if (use_fused_attn_x3(e, nq)) {
-      Prof pr(e, "attn_x3_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
-      launch_attn_x3_bwd((const float*)ba.qkv, (const float*)ba.o, (const float*)d_o, ba.lse, (float*)e->d_qkv, b, nq, c.heads,
-                         1.0f / std::sqrt((float)c.dim_head), e->stream);
-    } else if (use_fused_attn(e, nq)) {
-      // (class-row form: q, o, dO of one row per image; k, v read and d(q, k, v) written for every row)
-      const double live = cls_rows ? 1.0 / nq : 1.0;
-      Prof pr(e, "attn_bf16_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head * live, (double)rows * inner * (5 + 3 * live) * esz);
-      launch_attn_bf16_bwd((const bf16_t*)ba.qkv, (const bf16_t*)ba.o, (const bf16_t*)d_o, ba.lse, e->dsum, (bf16_t*)e->d_qkv, b, nq,
-                           c.heads, 1.0f / std::sqrt((float)c.dim_head), (const bf16_t*)e->zero_page, e->stream, cls_rows ? 1 : 0);
-    } else if (ba.attn_streamed) {   // the path this block's forward took (the flag may have been switched since: the saved state decides)
-      Prof pr(e, "attn_stream_bwd", 14.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 8 * esz);
-      launch_attn_stream_bwd((const bf16_t*)ba.qkv, (const bf16_t*)ba.o, (const bf16_t*)d_o, ba.lse, e->dsum, (bf16_t*)e->d_qkv, b, nq, c.heads,
-                             1.0f / std::sqrt((float)c.dim_head), e->stream);
-    } else {
-      int rc = ensure_scores(e, 4, (int64_t)b * c.heads * nq * round_up(nk, 4), err);
-      if (rc != VITX_OK) return rc;
-      attn_generic_bwd(e, bp, av, ag, b, &ba);
-    }
-    if (e->attn_dbias && !e->attn_bias.empty()) {   // regionvit.py:107 -- the bias is a variable: d(bias) = sum over the sequences of dS
-      Prof pr(e, "attn_dbias", 4.0 * b * c.heads * (double)nq * nq * c.dim_head, (double)rows * inner * 5 * esz);
-      launch_attn_dbias(ba.qkv, ba.o, d_o, ba.lse, T, b, nq, c.heads, 1.0f / std::sqrt((float)c.dim_head), e->attn_bias[(size_t)l], e->attn_bias_hs,
-                        e->attn_dbias_ws, e->attn_dbias, e->stream);
-    }
     EpiParams ep; ep.out = e->d_y; ep.ldo = d;
     ep.nt_out = (e->nt_mask >> 4) & 1;
-    const hipEvent_t fork_qkv = side_prefork(e);   // d(q, k, v) is complete
     dense_dgrad(e, e->d_qkv, 3 * inner, rows, bp.qkv, EPI_STORE, ep);
     dense_wgrad(e, ba.y1, d, e->d_qkv, 3 * inner, rows, bp.qkv, fork_qkv);
     side_note_read(e, e->rg_dqkv);
@@ -2447,7 +2440,7 @@ int engine_forward(vitx_engine* e, const float* img_dev, int b, int H, int W, in
     launch_dropout(x0, 0, (int64_t)b * ntok * d, emb_drop, seed, 0u, e->stream);                           // vit.py:166
   }
   draw_layer_dropout(e, seed);
-  const bool cls_rows = cls_rows_apply(e, ntok, extra, drop);   // the last block on the class rows only
+  const bool cls_rows = cls_rows_apply(e, b, ntok, extra, drop);   // the last block on the class rows only
   int rc;
   for (int l = 0; l < s0.depth; ++l) {
     if (!e->layer_kept[0][(size_t)l]) {   // cait.py:17-31,147: the whole block is skipped
